@@ -3,14 +3,14 @@
 
 Workload (Config B): 256 independent MPC instances PER GPU, horizon N=20, dt=0.05,
 apps/a1_configuration.yaml values, synthetic initial states (seeds 20240112+b, numpy MT19937).
-Protocol: 10 cold-start solves per instance (MPC::CreateInitialRun, untimed set-up), W warm-up RTI steps, then the timed
-region: K RTI steps with t_i = i*dt and state := node 1 of the previous trajectory (test/gait_opt_playground.cpp:113-126),
-device-resident (inputs are in HBM when the region starts), closed by the all-gather of the result records.  The region is
-repeated `--repeats` times back to back (the protocol simply continues): with the defaults that is BASELINE.md section 3.3's
-protocol, 10 cold starts then 100 CONSECUTIVE timed steps (5 regions of 20), and `value` = instances x (steps x repeats) /
-SUM of the regions -- the transient after the cold start included (the median region and the settled rate stand beside it,
-named as such).  One "step" = one RTI iteration of every instance of the batch (shift -> assemble -> condense -> QP solve ->
-line search -> trajectory update).
+Protocol: 10 cold-start solves per instance (MPC::CreateInitialRun, untimed set-up), W warm-up RTI steps, then K = `--steps` timed
+RTI steps with t_i = i*dt and state := node 1 of the previous trajectory (test/gait_opt_playground.cpp:113-126), device-resident
+(inputs are in HBM when a region starts), in `--repeats` consecutive timed regions of K / repeats steps, each closed by the
+all-gather of the result records.  With the defaults that is BASELINE.md section 3.3's 10 cold starts then 100 CONSECUTIVE timed
+steps, as one region; `value` = instances x steps / SUM of the regions and `ms_per_step` = SUM of the regions / steps -- the
+transient after the cold start included (the median region and the settled rate stand beside it, named as such).  One "step" =
+one RTI iteration of every instance of the batch (shift -> assemble -> condense -> QP solve -> line search -> trajectory update).
+`--dump-outputs DIR` writes the gathered result records of the last timed step as DIR/<name>.npy (float64), for comparing builds.
 
 Solver mode of the headline (`--mode`, default `lower_start`): EVERY solve ends by the reference's termination test (Clarabel's
 gap 1e-15 / feasibility 1e-10, clarabel_interface.cpp:165-175); in the K-step launches a solve is first attempted from the
@@ -157,6 +157,32 @@ def pmc_traffic(steps):
         return None, None
 
 
+# ---------- outputs of the timed path, for comparing builds ----------
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rec, m):
+    """The gathered result records of the last timed step -- what srbm_allgather_results hands a caller -- split by the record layout of
+    include/srbm_rti.h into DIR/record_header.npy (status, n, m, cost, alpha, err, qp_iters, init_time), primal.npy, dual.npy and
+    contact_times.npy (counts of the 4 feet, then 4 x 8 times), all float64, with instance.npy the global instance index of each row.  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of the instances is written."""
+    rec = np.asarray(rec, dtype=np.float64)
+    nx = 12 * (m.N + 1) + m.NUMAX
+    nm = 12 * (m.N + 1) + 6 * m.NSMAX + 16 * (m.N - 3) + 16
+    if rec.shape[1] != 8 + nx + nm + 36:
+        raise SystemExit('bench.py: result record of %d doubles, expected %d' % (rec.shape[1], 8 + nx + nm + 36))
+    rows = np.arange(rec.shape[0])
+    max_rows = max(1, DUMP_MAX_BYTES // (rec.shape[1] * 8 + 8))
+    if rec.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(rec.shape[0], max_rows, replace=False))
+    rec = rec[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    parts = {'instance': rows.astype(np.float64), 'record_header': rec[:, :8], 'primal': rec[:, 8:8 + nx], 'dual': rec[:, 8 + nx:8 + nx + nm],
+             'contact_times': rec[:, 8 + nx + nm:]}
+    for name, a in parts.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 # ---------- rank launcher ----------
 def free_port():
     s = socket.socket()
@@ -205,9 +231,12 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=100, help='timed RTI steps of the headline (in total, over all its regions)')
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps run back to back: value = instances x steps x repeats / their SUM')
+    ap.add_argument('--repeats', type=int, default=1, help='consecutive timed regions the --steps steps are split into (must divide --steps): '
+                                                          'value = instances x steps / SUM of the regions')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the result records of the last timed step of the headline (status header, primal, dual, contact times) as DIR/<name>.npy')
     ap.add_argument('--batch', type=int, default=BATCH_PER_GPU, help='instances per GPU')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--workload', choices=['B', 'D', 'E'], default='B',
@@ -236,6 +265,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1:
         raise SystemExit('bench.py: --gpus, --steps and --repeats must be positive')
+    if args.steps % args.repeats:
+        raise SystemExit('bench.py: --repeats must divide --steps')
+    region_steps = args.steps // args.repeats                 # RTI steps of one timed region (one launch of the fused kernel)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -407,7 +439,7 @@ def main():
         el, nrep = r['elapsed'], len(r['region_s'])
         m = r['mpc']
         ts, mu = m.solver_step_rule()
-        return {'workload': label, 'mode': r['mode'], 'value': r['n_inst'] * steps * nrep / el, 'unit': 'it/s', 'ms_per_step': 1e3 * el / (steps * nrep), 'steps': steps, 'repeats': nrep,
+        return {'workload': label, 'mode': r['mode'], 'value': r['n_inst'] * steps * nrep / el, 'unit': 'it/s', 'ms_per_step': 1e3 * el / (steps * nrep), 'steps': steps * nrep, 'repeats': nrep,
                 'statistic': 'instances x steps x repeats / SUM of the regions (consecutive steps after the cold start)',
                 'value_from_median_region': r['n_inst'] * steps / r['median_region'],
                 'region_ms': [1e3 * v for v in r['region_s']], 'batch_per_gpu': r['hi'] - r['lo'], 'global_batch': r['n_inst'], 'num_nodes': m.N,
@@ -425,7 +457,9 @@ def main():
                               'caller of the mpc:: facade gets)',
                  'step_rule': 'solves end by the STEP RULE (tol_step 1e-5: the affine Newton step bounds the distance to the minimiser) -- a looser termination '
                               'than the reference\'s gap 1e-15 -- with the lower starting point (srbm_set_solver_step_rule(1e-5, 0.1))'}
-    main = run_protocol(cfg, make_instance, B, args.workload == 'E', MODE, args.warmup, args.steps, args.repeats)
+    main = run_protocol(cfg, make_instance, B, args.workload == 'E', MODE, args.warmup, region_steps, args.repeats)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main['allrec'].cpu().numpy(), main['mpc'])
     mpc, states, ees = main['mpc'], main['states'], main['ees']
     region_s, region_work, med, elapsed = main['region_s'], main['region_work'], main['med'], main['elapsed']
     k3_each = main['launch_ms']; k3_launches = len(k3_each)
@@ -437,14 +471,14 @@ def main():
     if args.workload == 'B' and not args.no_other_modes:
         for mo in ('reference', 'lower_start', 'step_rule'):
             if mo != MODE:
-                rr = run_protocol(cfg, make_instance, B, False, mo, args.warmup, args.steps, args.repeats)
-                other[mo] = summary(rr, args.steps, 'Config B, same protocol: ' + MODE_TEXT[mo])
+                rr = run_protocol(cfg, make_instance, B, False, mo, args.warmup, region_steps, args.repeats)
+                other[mo] = summary(rr, region_steps, 'Config B, same protocol: ' + MODE_TEXT[mo])
                 del rr
-        # the same steps of the headline's mode as ONE region (one launch of steps x repeats steps, one all-gather): what the four synchronisation
-        # points between the regions of `value` cost -- at each of them the batch waits for the instance whose 20 solves happened to be the longest
+        # the same steps of the headline's mode as ONE region (one launch of all the steps, one all-gather): what the synchronisation points
+        # between the regions of `value` cost -- at each of them the batch waits for the instance whose solves happened to be the longest
         if args.repeats > 1:
-            rr = run_protocol(cfg, make_instance, B, False, MODE, args.warmup, args.steps * args.repeats, 1)
-            other['one_region'] = summary(rr, args.steps * args.repeats, 'Config B, the %d steps of `value` as ONE timed region (one launch): ' % (args.steps * args.repeats) + MODE_TEXT[MODE])
+            rr = run_protocol(cfg, make_instance, B, False, MODE, args.warmup, args.steps, 1)
+            other['one_region'] = summary(rr, args.steps, 'Config B, the %d steps of `value` as ONE timed region (one launch): ' % args.steps + MODE_TEXT[MODE])
             del rr
     # ---- BASELINE configs 4 and 5 at their per-GPU sizes, the same protocol with the same --steps / --warmup / --repeats, in the headline's mode
     # (Config D also in the step-rule mode: the number rounds 3-4 tracked) ----
@@ -453,16 +487,16 @@ def main():
         cfg_d = host.load_config('a1_config_distr_rejection')
         d_label = ('Config D: 512 A1 SRBM MPC instances per GPU, N=50, dt=0.02, a1_config_distr_rejection.yaml values, push distribution on the '
                    'initial momentum; not-solved solves belong to instances whose QPs the oracle finds infeasible too')
-        rd = run_protocol(cfg_d, config_d_instance, 512, False, MODE, args.warmup, args.steps, args.repeats)
-        d_stats = summary(rd, args.steps, d_label)
+        rd = run_protocol(cfg_d, config_d_instance, 512, False, MODE, args.warmup, region_steps, args.repeats)
+        d_stats = summary(rd, region_steps, d_label)
         del rd
         if MODE != 'step_rule':
-            rd = run_protocol(cfg_d, config_d_instance, 512, False, 'step_rule', args.warmup, args.steps, args.repeats)
-            d_stats['step_rule_mode'] = summary(rd, args.steps, d_label)
+            rd = run_protocol(cfg_d, config_d_instance, 512, False, 'step_rule', args.warmup, region_steps, args.repeats)
+            d_stats['step_rule_mode'] = summary(rd, region_steps, d_label)
             del rd
         cfg_e = host.load_config('a1_configuration', num_nodes=40)
-        re_ = run_protocol(cfg_e, config_b_instance, 128, True, MODE, args.warmup, args.steps, args.repeats)
-        e_stats = summary(re_, args.steps, 'Config E (SRBM stand-in for the dead centroidal MPC): 128 instances per GPU, N=40, dt=0.05, LARGE-capacity build')
+        re_ = run_protocol(cfg_e, config_b_instance, 128, True, MODE, args.warmup, region_steps, args.repeats)
+        e_stats = summary(re_, region_steps, 'Config E (SRBM stand-in for the dead centroidal MPC): 128 instances per GPU, N=40, dt=0.05, LARGE-capacity build')
         del re_
 
     # ---- second segment (Config C): N=20 / dt=0.05 with the values of apps/a1_gait_opt_config.yaml, gait step every 5th iteration.
@@ -627,14 +661,14 @@ def main():
                                                  'srbm_qp_control_dev; contact forces stacked on the device): no copy, no synchronisation inside a tick',
                                          'ms_per_tick_of_the_batch': 1e3 * el_d / args.wbc_ticks, 'control_actions_per_s': n_inst * args.wbc_ticks / el_d,
                                          'targets_not_ok': int(bad_d[0]), 'qp_not_solved': int(bad_d[1])}}
-    value = n_inst * args.steps * args.repeats / elapsed          # `elapsed` = SUM of the timed regions
+    value = n_inst * args.steps / elapsed          # `elapsed` = SUM of the timed regions
 
-    # ---- the headline's protocol CONTINUED on the same batch: `repeats` more regions of `steps` steps from step `--steady-from` on.  The five
-    # regions of the headline cover the first ~100 steps after the cold start, where the lower-start attempts still fail more often and the
+    # ---- the headline's protocol CONTINUED on the same batch: `steps` more steps in `repeats` regions from step `--steady-from` on.  The
+    # regions of the headline cover the first steps after the cold start, where the lower-start attempts still fail more often and the
     # solves are longer; a controller that runs for seconds sees the rate below.  Reported beside `value`, never instead of it ----
     steady = None
     if args.steady_from > 0 and args.workload == 'B':
-        first_s = args.warmup + args.steps * args.repeats
+        first_s = args.warmup + args.steps
         if args.steady_from > first_s:
             mpc.rti_advance(first_s, args.steady_from - first_s)          # untimed
             first_s = args.steady_from
@@ -647,20 +681,20 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             t0s = time.perf_counter()
-            mpc.rti_advance(first_s, args.steps)
+            mpc.rti_advance(first_s, region_steps)
             gather_dev(mpc, rec_s, rec_s_mine)
             torch.cuda.synchronize()
             if DIST:
                 dist.barrier()
             reg_steady.append(max_over_ranks(time.perf_counter() - t0s))
-            first_s += args.steps
+            first_s += region_steps
         el_s = float(np.sum(reg_steady))
         st_s, err_s = mpc.status()
-        steady = {'value': n_inst * args.steps * args.repeats / el_s, 'unit': 'it/s', 'ms_per_step': 1e3 * el_s / (args.steps * args.repeats), 'region_ms': [1e3 * v for v in reg_steady],
-                  'first_step': first_s - args.steps * args.repeats, 'statistic': 'instances x steps x repeats / SUM of %d regions of %d steps, same bracket as the headline' % (args.repeats, args.steps),
+        steady = {'value': n_inst * args.steps / el_s, 'unit': 'it/s', 'ms_per_step': 1e3 * el_s / args.steps, 'region_ms': [1e3 * v for v in reg_steady],
+                  'first_step': first_s - args.steps, 'statistic': 'instances x steps / SUM of %d regions of %d steps, same bracket as the headline' % (args.repeats, region_steps),
                   'all_solved_after': bool(np.all(st_s <= 1) and np.all(err_s == 0)),
                   'note': 'the protocol of `value` continued on the same batch past the transient after the cold start (its regions are steps %d..%d); '
-                          '`value` and `roofline` describe the regions of the headline only' % (args.warmup, args.warmup + args.steps * args.repeats)}
+                          '`value` and `roofline` describe the regions of the headline only' % (args.warmup, args.warmup + args.steps)}
 
     # this rank's own region times, gathered: a straggling GPU shows up here, not only in the max
     per_rank_ms = [[1e3 * v for v in main['region_local_s']]]
@@ -682,7 +716,7 @@ def main():
         mfma_per_launch = float(np.mean([w_[2] for w_ in region_work[:n_l]])) if n_l else 0.0
         achieved = flops_per_launch / k3_avg_s / 1e12 if k3_avg_s > 0 else 0.0
         exec_tflops = mfma_per_launch * MFMA_FLOP / k3_avg_s / 1e12 if k3_avg_s > 0 else 0.0
-        traffic, pmc = pmc_traffic(args.steps) if args.workload == 'B' else (None, None)
+        traffic, pmc = pmc_traffic(region_steps) if args.workload == 'B' else (None, None)
         # `bound` keeps to the schema of the measurement contract (hbm | mfma): it names the roof `frac` is priced against.  What limits the
         # kernel in practice is neither -- `limiter` says so in one word, `limiter_detail` in a sentence
         roof = {'bound': 'mfma', 'limiter': 'latency',
@@ -693,7 +727,7 @@ def main():
                 'kernel': ('srbm_rti_fused' if cfg['num_nodes'] <= 22 else 'srbm_rti_fused_long') + (' (LARGE build)' if mpc.large else ''),
                 'achieved': achieved, 'peak': FP64_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / FP64_PEAK_TFLOPS,
                 'achieved_is': 'ALGORITHMIC flops (SURVEY.md 8d formula at the sizes and IPM iteration counts executed) / measured launch time',
-                'traffic': traffic, 'avg_launch_ms': k3_avg_s * 1e3, 'launches_timed': k3_launches, 'ipm_iterations_per_solve': float(np.mean([w_[0] for w_ in region_work[:n_l]])) / max(1, (hi - lo) * args.steps) if n_l else 0.0,
+                'traffic': traffic, 'avg_launch_ms': k3_avg_s * 1e3, 'launches_timed': k3_launches, 'ipm_iterations_per_solve': float(np.mean([w_[0] for w_ in region_work[:n_l]])) / max(1, (hi - lo) * region_steps) if n_l else 0.0,
                 'algorithmic_flops_per_launch': flops_per_launch,
                 'executed_mfma_tflops': exec_tflops, 'executed_mfma_frac_of_peak': exec_tflops / FP64_PEAK_TFLOPS,
                 'executed_mfma_instructions_per_launch': mfma_per_launch}
@@ -705,12 +739,12 @@ def main():
         out = {
             'metric': 'MPC RTI iterations/sec (batched A1 SRBM, N=%d)' % cfg['num_nodes'],
             'value': value, 'unit': 'it/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': 1e3 * elapsed / (args.steps * args.repeats), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f64', 'data': 'synthetic', 'repeats': args.repeats, 'region_ms': [1e3 * v for v in region_s],
-            'statistic': 'value = instances x (steps x repeats) / SUM of the timed regions (max over ranks each): %d CONSECUTIVE RTI steps after the 10 cold starts '
-                         'and the warm-up, the transient of the first region included (BASELINE.md section 3.3)' % (args.steps * args.repeats),
+            'statistic': 'value = instances x steps / SUM of the timed regions (max over ranks each): %d CONSECUTIVE RTI steps in %d region(s) after the 10 '
+                         'cold starts and the warm-up, the transient of the first region included (BASELINE.md section 3.3)' % (args.steps, args.repeats),
             'solver_mode': MODE, 'solver_mode_is': MODE_TEXT[MODE],
-            'median_region': {'value': n_inst * args.steps / main['median_region'], 'ms_per_step': 1e3 * main['median_region'] / args.steps,
+            'median_region': {'value': n_inst * region_steps / main['median_region'], 'ms_per_step': 1e3 * main['median_region'] / region_steps,
                               'note': 'instances x steps / MEDIAN region: the settled rate of the same run (rounds 1-4 reported this as `value`)'},
             'collective': {'path': ('C-ABI: srbm_allgather_results (in-place ncclAllGather on the batch stream, communicator from srbm_rccl_comm_init_rank)'
                                     if coll['kind'] == 'cabi' else coll['kind'] if not DIST else 'torch.distributed all_gather_into_tensor (backend nccl = RCCL)'),

@@ -105,6 +105,7 @@ int main(int argc, char** argv) {
     const std::string urdf = argc > 1 ? argv[1] : "-";
     const int ticks = argc > 2 ? std::atoi(argv[2]) : 8;
     const int freq = argc > 3 ? std::atoi(argv[3]) : 5;
+    const std::string out_dir = argc > 4 ? argv[4] : ".";       // where the log, the statistics and the trajectory dump are written
     mpc::MPCInfo info;
     info.num_nodes = kNumNodes; info.integrator_dt = kDt; info.friction_coef = kMu; info.force_bound = kForceBound;
     info.swing_height = kSwing; info.foot_offset = kFootOffset; info.force_cost = kForceCost;
@@ -128,7 +129,7 @@ int main(int argc, char** argv) {
     Mat Q = Mat::Zero(12, 12);
     for (int i = 0; i < 12; i++) Q(i, i) = kQdiag[i];
     const std::vector<Vec> warm(kNumNodes + 1, init);
-    ControllerLoop c(info, urdf, urdf == "-" ? &consts : nullptr, warm, goal, Q, freq, "/tmp/mpc_facade_log.txt");
+    ControllerLoop c(info, urdf, urdf == "-" ? &consts : nullptr, warm, goal, Q, freq, out_dir + "/mpc_facade_log.txt");
     const Feet ee0 = {{0.2, 0.2, 0}, {0.2, -0.2, 0}, {-0.2, 0.2, 0}, {-0.2, -0.2, 0}};
     c.start(init, ee0);
     c.contacts = c.plan.GetDesiredContacts(0.0);
@@ -165,10 +166,10 @@ int main(int argc, char** argv) {
     for (int ee = 0; ee < 4; ee++) std::printf("box_center %d %.17g\nbox_center %d %.17g\n", 2 * ee, bc[ee](0), 2 * ee + 1, bc[ee](1));
     // statistics and trajectory dumps (mpc.cpp:818-899 PrintStats over the whole history, trajectory.cpp:146-223 PrintTrajectoryToFile)
     {
-        std::ofstream stats("/tmp/mpc_facade_stats.txt");
+        std::ofstream stats(out_dir + "/mpc_facade_stats.txt");
         c.solver.PrintStats(stats);
     }
-    t.PrintTrajectoryToFile("/tmp/mpc_facade_traj.txt");
+    t.PrintTrajectoryToFile(out_dir + "/mpc_facade_traj.txt");
     const Vec sv = t.SplinesAsVec();
     std::printf("recorded 0 %d\n", c.solver.GetNumRecordedSolves());
     for (int i = 0; i < (int)sv.size(); i++) std::printf("spline_vec %d %.17g\n", i, sv(i));

@@ -45,8 +45,10 @@ def test_code_object_is_gfx950(libpath):
 
 
 def test_no_gpu_fails_loudly(libpath):
-    import torch
-    if torch.cuda.is_available():
+    # GPU presence is asked in a child process: importing torch here would load torch's own HIP runtime beside the library's, and once torch
+    # has opened the GPU the library's runtime finds no device for the GPU tests that run later in this process
+    r = subprocess.run([sys.executable, '-c', 'import sys, torch; sys.exit(0 if torch.cuda.is_available() else 3)'], capture_output=True, timeout=300)
+    if r.returncode == 0:
         pytest.skip('GPU present')
     cfg = host.load_config()
     with pytest.raises(RuntimeError):
@@ -125,6 +127,34 @@ def test_bench_dry_run_eight_ranks_config_d():
     assert d['n_gpus'] == 8 and d['collective_world_size'] == 8 and d['scaling'] == 'weak'
     assert c['batch_per_gpu'] == 512 and c['global_batch'] == 4096 and c['records_gathered'] == 4096 and c['gather_ok']
     assert c['shard_bounds'] == [[512 * r_, 512 * (r_ + 1)] for r_ in range(8)]
+
+
+def test_bench_dump_outputs_split_the_records_and_sample_a_fixed_subset(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the gathered result records split by the layout of include/srbm_rti.h (header, primal, dual, contact times)
+    into float64 .npy files; above the size cap a seeded subset of the instances, the same on every run"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class M:
+        N, NUMAX, NSMAX = 20, 160, 120                       # the standard build's capacities
+    ld = 8 + 12 * 21 + 160 + 12 * 21 + 6 * 120 + 16 * 17 + 16 + 36
+    rec = np.arange(300 * ld, dtype=np.float64).reshape(300, ld)
+    names = ['record_header', 'primal', 'dual', 'contact_times']
+    load = lambda d: {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    bench.dump_outputs(str(tmp_path / 'all'), rec, M)
+    a = load(str(tmp_path / 'all'))
+    assert sorted(a) == sorted(names + ['instance']) and all(v.dtype == np.float64 for v in a.values())
+    assert a['record_header'].shape == (300, 8) and a['contact_times'].shape == (300, 36) and a['primal'].shape == (300, 12 * 21 + 160)
+    assert np.array_equal(np.hstack([a[k] for k in names]), rec) and np.array_equal(a['instance'], np.arange(300))
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 100 * (ld * 8 + 8))
+    bench.dump_outputs(str(tmp_path / 's1'), rec, M)
+    bench.dump_outputs(str(tmp_path / 's2'), rec, M)
+    s1, s2 = load(str(tmp_path / 's1')), load(str(tmp_path / 's2'))
+    rows = s1['instance'].astype(int)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and sum(v.nbytes for v in s1.values()) <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(np.hstack([s1[k] for k in names]), rec[rows]) and all(np.array_equal(s1[k], s2[k]) for k in s1)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'bad'), rec[:, :-1], M)
 
 
 def test_build_is_serialised_by_a_file_lock():

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,12 +19,13 @@ def free_port():
     return p
 
 
-def test_bench_line_under_torchrun_with_the_collective_path():
+def test_bench_line_under_torchrun_with_the_collective_path(tmp_path):
     env = dict(os.environ, SRBM_BENCH_FORCE_DIST='1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', str(free_port()),
-           os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--repeats', '2', '--gait-steps', '10', '--closed-loop-steps', '4', '--wbc-ticks', '3']
+           os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2', '--repeats', '2', '--gait-steps', '10', '--closed-loop-steps', '4', '--wbc-ticks', '3',
+           '--dump-outputs', str(tmp_path / 'out')]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -31,9 +33,9 @@ def test_bench_line_under_torchrun_with_the_collective_path():
     d = json.loads(lines[0])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
-    assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['higher_is_better'] is True and d['scaling'] == 'weak'
+    assert d['n_gpus'] == 1 and d['steps'] == 8 and d['warmup'] == 2 and d['higher_is_better'] is True and d['scaling'] == 'weak'
     assert d['unit'] == 'it/s' and d['dtype'] == 'f64' and d['data'] == 'synthetic' and d['vs_baseline'] is None
-    assert d['value'] > 1e4 and abs(d['value'] - 256 * 4 / (d['ms_per_step'] * 4 * 1e-3)) < 1e-6 * d['value']
+    assert d['value'] > 1e4 and abs(d['value'] - 256 * 8 / (d['ms_per_step'] * 8 * 1e-3)) < 1e-6 * d['value']
     # the headline: every solve ends by the reference's criterion (lower starting point); the step-rule mode and the library default stand beside it
     assert d['solver_mode'] == 'lower_start' and d['config']['solver']['tol_step'] == 0.0 and d['config']['solver']['start_mu'] > 0
     assert d['config']['solver']['solves_ended_by_step_rule'] == 0
@@ -43,7 +45,8 @@ def test_bench_line_under_torchrun_with_the_collective_path():
     assert d['collective']['path'].startswith('C-ABI') and d['collective']['note'] is None and d['rccl_world_size'] == 1
     c = d['config']
     assert 'workload' in c and c['global_batch'] == 256 and c['records_gathered'] == 256 and 'model' not in c
-    assert c['timed_solves'] == 256 * 4 * 2 and c['err_bits_all_timed_steps'] == 0
+    assert c['timed_solves'] == 256 * 8 and c['err_bits_all_timed_steps'] == 0        # --steps = ALL timed steps (2 regions of 4)
+    assert len(d['region_ms']) == 2 and abs(sum(d['region_ms']) - 8 * d['ms_per_step']) < 1e-9 * sum(d['region_ms'])
     rf = d['roofline']
     for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic'):
         assert k in rf, k
@@ -55,6 +58,19 @@ def test_bench_line_under_torchrun_with_the_collective_path():
     assert d['gait']['err_bits_all_steps'] == 0 and d['closed_loop']['plant_finite'] and d['wbc']['finite']
     ss = d['steady_state']        # the headline's protocol continued past the transient after the cold start (bench.py --steady-from)
     assert ss['first_step'] == 125 and ss['all_solved_after'] and len(ss['region_ms']) == 2 and ss['value'] > 1e4
+    # --dump-outputs: the gathered result records of the last timed step, split by the record layout of include/srbm_rti.h
+    out = {f[:-4]: np.load(str(tmp_path / 'out' / f)) for f in os.listdir(str(tmp_path / 'out'))}
+    assert sorted(out) == ['contact_times', 'dual', 'instance', 'primal', 'record_header']
+    assert all(a.dtype == np.float64 and a.shape[0] == 256 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    hdr = out['record_header']
+    assert np.array_equal(out['instance'], np.arange(256)) and hdr.shape == (256, 8) and out['contact_times'].shape == (256, 36)
+    assert np.all(hdr[:, 5] == 0) and np.all(np.isfinite(out['primal'])) and np.all(np.isfinite(out['dual']))
+    for b in range(256):                                     # x[0..n) and z[0..m), zero padded
+        n, m = int(hdr[b, 1]), int(hdr[b, 2])
+        assert 0 < n <= out['primal'].shape[1] and 0 < m <= out['dual'].shape[1] and np.abs(out['primal'][b, :n]).max() > 0
+        assert not out['primal'][b, n:].any() and not out['dual'][b, m:].any()
+    counts = out['contact_times'][:, :4]
+    assert np.array_equal(counts, np.round(counts)) and counts.min() >= 0 and counts.max() <= 8
 
 
 def run_bench(*args):
@@ -74,9 +90,9 @@ def test_config_d_full_per_gpu_share_through_the_bench():
     d = run_bench('--workload', 'D', '--no-cpu-baseline', '--closed-loop-steps', '0')
     c = d['config']
     assert c['batch_per_gpu'] == 512 and c['num_nodes'] == 50 and c['records_gathered'] == 512
-    assert c['timed_solves'] == 512 * d['steps'] * d['repeats'] and c['err_bits_all_timed_steps'] == 0 and c['max_iter_in_timed_solves'] == 0
+    assert c['timed_solves'] == 512 * d['steps'] and c['err_bits_all_timed_steps'] == 0 and c['max_iter_in_timed_solves'] == 0
     assert set(c['instances_with_a_solve_not_solved_rank0']) <= {150, 441}, c['instances_with_a_solve_not_solved_rank0']
-    assert c['not_solved_in_timed_solves'] <= 2 * d['steps'] * d['repeats']
+    assert c['not_solved_in_timed_solves'] <= 2 * d['steps']
     assert d['value'] > 4e4, d['value']
     assert d['roofline']['kernel'].startswith('srbm_rti_fused_long')
 
@@ -87,5 +103,5 @@ def test_config_e_full_per_gpu_share_through_the_bench():
     d = run_bench('--workload', 'E', '--no-cpu-baseline', '--closed-loop-steps', '0')
     c = d['config']
     assert c['batch_per_gpu'] == 128 and c['num_nodes'] == 40 and c['records_gathered'] == 128
-    assert c['timed_solves'] == 128 * d['steps'] * d['repeats'] and c['all_solved'] and c['err_bits_all_timed_steps'] == 0
+    assert c['timed_solves'] == 128 * d['steps'] and c['all_solved'] and c['err_bits_all_timed_steps'] == 0
     assert '(LARGE build)' in d['roofline']['kernel'] and d['value'] > 5e3

@@ -1,5 +1,5 @@
-"""Builds, AT TEST TIME and in the build container only, translation units that hold the reference's own caller code -- cut out of
-/root/reference as text, never stored in this repository -- between a builder-written prologue (includes, the two visualiser types and the
+"""Builds translation units that hold the reference's own caller code -- cut out of a checkout of the reference as text, never stored in
+this repository -- between a builder-written prologue (includes, the two visualiser types and the
 Catch2 / timer names the callers mention, a class shell with the members the controller's methods touch) and compiles them against
 include/mpc_facade/mpc.h.  What it checks is SURVEY.md section 8(b): the callers of the hot path compile UNCHANGED against the facade.
 
@@ -7,7 +7,9 @@ include/mpc_facade/mpc.h.  What it checks is SURVEY.md section 8(b): the callers
                     test/mpc_test.cpp: the body of SECTION("Model Partials") as the body of a function with the section's free variables as arguments
   controller unit   controllers/mpc_controller.cpp: MPCController::MPCUpdate and MPCController::GaitOpt as members of a class shell
 
-    write_units(reference_root, out_dir) -> [paths]      (raises FileNotFoundError when the reference is not there: the test then skips)
+    write_units(reference_root, out_dir) -> [paths]      (raises FileNotFoundError when the reference is not there)
+
+    python tests/tools/extract_callsites.py <reference checkout> [out_dir]
 """
 import os
 import re
@@ -187,4 +189,6 @@ def write_units(reference_root, out_dir):
 
 if __name__ == '__main__':
     import sys
-    print('\n'.join(write_units(sys.argv[1] if len(sys.argv) > 1 else '/root/reference', sys.argv[2] if len(sys.argv) > 2 else '.')))
+    if len(sys.argv) < 2:
+        sys.exit('usage: extract_callsites.py <reference checkout> [out_dir]')
+    print('\n'.join(write_units(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else '.')))

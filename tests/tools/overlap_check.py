@@ -1,13 +1,12 @@
 """Line-overlap of files in this repository with the reference's sources (the measure VERDICT r4 used: whitespace-normalised lines of at least 25
-characters, comments and includes left out, against every source file of the reference).  Build container only: needs /root/reference.
+characters, comments and includes left out, against every source file of the reference).  Needs a checkout of the reference.
 
-    python tests/tools/overlap_check.py tests/cpp/*.cpp            # prints matched / counted lines per file
+    python tests/tools/overlap_check.py <reference checkout> tests/cpp/*.cpp            # prints matched / counted lines per file
 """
 import os
 import re
 import sys
 
-REF = '/root/reference'
 EXT = ('.cpp', '.h', '.hpp', '.cc', '.py', '.c', '.cu', '.hip')
 
 
@@ -23,9 +22,9 @@ def norm_lines(text):
     return out
 
 
-def reference_lines():
+def reference_lines(reference_root):
     ref = set()
-    for d, _, files in os.walk(REF):
+    for d, _, files in os.walk(reference_root):
         if '/.git' in d:
             continue
         for f in files:
@@ -44,9 +43,9 @@ def overlap(path, ref):
 
 
 if __name__ == '__main__':
-    if not os.path.isdir(REF):
-        sys.exit('reference not present')
-    ref = reference_lines()
-    for p in sys.argv[1:]:
+    if len(sys.argv) < 2 or not os.path.isdir(sys.argv[1]):
+        sys.exit('usage: overlap_check.py <reference checkout> FILE...')
+    ref = reference_lines(sys.argv[1])
+    for p in sys.argv[2:]:
         h, n = overlap(p, ref)
         print('%-60s %4d / %4d  %5.1f %%' % (p, h, n, 100.0 * h / max(n, 1)))
