@@ -19,11 +19,6 @@
 #include "srbm_wbc.hiph"
 #include "../../include/srbm_rti.h"
 
-#ifdef SRBM_LARGE
-#define SRBM_DYN_LDS(T) sizeof(T)        /* LARGE build: the working sets of kernels 1, 2, 4 exceed 64 KB of static LDS */
-#else
-#define SRBM_DYN_LDS(T) 0
-#endif
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return -1; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
@@ -52,7 +47,6 @@ struct srbm_batch {
     bool push_set = false;
     hipStream_t stream = nullptr;
     bool owns_stream = true;
-    size_t k3_lds = 0;
     int n_cu = 0;
     SrbmQueue* queues = nullptr;     // step queues of multi-step launches of a batch larger than the chip (srbm_fused.hiph), allocated at first use
     bool queued_ok = true;           // SRBM_NO_STEP_QUEUE=1 in the environment: such launches as one workgroup per instance (A/B, tests)
@@ -347,14 +341,14 @@ static int launch_step(srbm_batch* h, bool exact = false) {
     const double tol_step = exact ? 0.0 : h->hp.tol_step, start_mu = 0.0;
     h->last_tol_step = tol_step;
     const int B = h->batch;
-    hipLaunchKernelGGL(srbm_k1_assemble, dim3(B), dim3(K1_THREADS), SRBM_DYN_LDS(K1Shared), h->stream, h->dp, h->insts, h->works, h->d_state, h->d_time, h->d_ee);
-    hipLaunchKernelGGL(srbm_k2_condense, dim3(B), dim3(K2_THREADS), SRBM_DYN_LDS(K2Shared), h->stream, h->dp, h->insts, h->works);
+    hipLaunchKernelGGL(srbm_k1_assemble, dim3(B), dim3(K1_THREADS), 0, h->stream, h->dp, h->insts, h->works, h->d_state, h->d_time, h->d_ee);
+    hipLaunchKernelGGL(srbm_k2_condense, dim3(B), dim3(K2_THREADS), 0, h->stream, h->dp, h->insts, h->works);
     const bool tm = h->timing && h->ev_used < h->ev_start.size();
     if (tm) HIPCHK(hipEventRecord(h->ev_start[h->ev_used], h->stream));
-    if (h->hp.N <= K3_SHORT_N) hipLaunchKernelGGL(srbm_k3_ipm, dim3(B), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
-    else hipLaunchKernelGGL(srbm_k3_ipm_long, dim3(B), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
+    if (h->hp.N <= K3_SHORT_N) hipLaunchKernelGGL(srbm_k3_ipm, dim3(B), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
+    else hipLaunchKernelGGL(srbm_k3_ipm_long, dim3(B), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = 1; h->ev_used++; }
-    hipLaunchKernelGGL(srbm_k4_update, dim3(B), dim3(K4_THREADS), SRBM_DYN_LDS(K4Shared), h->stream, h->dp, h->insts, h->works);
+    hipLaunchKernelGGL(srbm_k4_update, dim3(B), dim3(K4_THREADS), 0, h->stream, h->dp, h->insts, h->works);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -379,15 +373,22 @@ int srbm_debug_get_profile2(srbm_batch* h, int inst, double* out96) {
     HIPCHK(hipMemcpy(out96, reinterpret_cast<const char*>(h->works + inst) + offsetof(SrbmWork, prof2), sizeof(double) * 96, hipMemcpyDeviceToHost));
     return 0;
 }
+// LDS map of the unit-test hooks of the dense building blocks (doubles into srbm_lds): the packed matrix, the Cholesky panel, x, t, xc, the int
+// column map.  Each hook is launched with the LDS up to the end of the last array it uses.  The map starts 16 doubles in: with the matrix and
+// the panel where the IPM has them (K3Smem: 0 and SRBM_HPACK), every call of the dense helpers would pass the same LDS addresses, the compiler
+// propagates them into the helpers as constants, and the IPM's factorisation gets slower (Cholesky +4 % of its ticks; docs/history.md).
+struct DbgLds {
+    static constexpr int M = 16, PANEL = M + SRBM_HPACK, X = PANEL + DN_PANEL_DOUBLES, T = X + SRBM_NUMAX, XC = T + SRBM_NUMAX, MAP = XC + SRBM_NUMAX,
+                         END = MAP + (SRBM_NUMAX + 1) / 2;
+};
 // unit-test hook for the dense building blocks: Cholesky of `count` packed lower-triangular n x n matrices, one workgroup each
 __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve(int n, const double* __restrict__ Min, const double* __restrict__ rhs,
                                                                double* __restrict__ xout, double* __restrict__ Xout, int* __restrict__ ticks) {
-    extern __shared__ double dbg_smem2[];
     const int np = n * (n + 1) / 2;
-    double* M = dbg_smem2;
-    double* panel = dbg_smem2 + (size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2;
-    double* xv = panel + DN_PANEL_DOUBLES;
-    double* tv = xv + SRBM_NUMAX;
+    double* M = srbm_lds + DbgLds::M;
+    double* panel = srbm_lds + DbgLds::PANEL;
+    double* xv = srbm_lds + DbgLds::X;
+    double* tv = srbm_lds + DbgLds::T;
     const double* src = Min + (size_t)blockIdx.x * np;
     for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
     for (int e = threadIdx.x; e < n; e += DN_THREADS) xv[e] = rhs[(size_t)blockIdx.x * n + e];
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve(int n, const do
     const long long t0 = (long long)__builtin_amdgcn_s_memtime();
     dn_trtri(M, n, panel);
     const long long t1 = (long long)__builtin_amdgcn_s_memtime();
-    dn_solve_inv(0, n, (int)(xv - dbg_smem2), (int)(tv - dbg_smem2), -1, 0, 0
+    dn_solve_inv(DbgLds::M, n, DbgLds::X, DbgLds::T, -1, 0, 0
 #ifdef SRBM_M_GLOBAL
                  , M
 #endif
@@ -411,10 +412,9 @@ __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve(int n, const do
     if (threadIdx.x == 0) { ticks[2 * blockIdx.x] = (int)(t1 - t0); ticks[2 * blockIdx.x + 1] = (int)(t2 - t1); }
 }
 __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_cholesky(int n, const double* __restrict__ Min, double* __restrict__ Lout, int* __restrict__ nreg_out) {
-    extern __shared__ double dbg_smem[];
     const int np = n * (n + 1) / 2;
-    double* M = dbg_smem;
-    double* panel = dbg_smem + (size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2;
+    double* M = srbm_lds + DbgLds::M;
+    double* panel = srbm_lds + DbgLds::PANEL;
     const double* src = Min + (size_t)blockIdx.x * np;
     for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
     __syncthreads();
@@ -432,14 +432,11 @@ __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_cholesky(int n, const
 // the column map, factor + inverse of the mapped block, solve with the gather / scatter through the map; unmapped entries of x keep rhs
 __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve_mapped(int n, int nc, const int* __restrict__ map, const double* __restrict__ Min,
                                                                       const double* __restrict__ rhs, double* __restrict__ xout, int* __restrict__ nreg_out) {
-    extern __shared__ double dbg_smem3[];
     const int np = n * (n + 1) / 2;
-    double* M = dbg_smem3;
-    double* panel = dbg_smem3 + (size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2;
-    double* xv = panel + DN_PANEL_DOUBLES;
-    double* tv = xv + SRBM_NUMAX;
-    double* xc = tv + SRBM_NUMAX;
-    int* imap = reinterpret_cast<int*>(xc + SRBM_NUMAX);
+    double* M = srbm_lds + DbgLds::M;
+    double* panel = srbm_lds + DbgLds::PANEL;
+    double* xv = srbm_lds + DbgLds::X;
+    int* imap = reinterpret_cast<int*>(srbm_lds + DbgLds::MAP);
     const double* src = Min + (size_t)blockIdx.x * np;
     for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
     for (int e = threadIdx.x; e < n; e += DN_THREADS) xv[e] = rhs[(size_t)blockIdx.x * n + e];
@@ -451,7 +448,7 @@ __global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve_mapped(int n, i
     dn_cholesky(T, M, nc, panel, &nreg);
     chol_invert_diag_blocks(M, nc, panel);
     dn_trtri(M, nc, panel);
-    dn_solve_inv(0, nc, (int)(xv - dbg_smem3), (int)(tv - dbg_smem3), (int)(reinterpret_cast<double*>(imap) - dbg_smem3), (int)(xc - dbg_smem3), 0
+    dn_solve_inv(DbgLds::M, nc, DbgLds::X, DbgLds::T, DbgLds::MAP, DbgLds::XC, 0
 #ifdef SRBM_M_GLOBAL
                  , M
 #endif
@@ -472,7 +469,7 @@ int srbm_debug_solve_mapped(int n, int nc, const int* map, int count, const doub
     HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dr, rhs, vb, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dmap, map, sizeof(int) * nc, hipMemcpyHostToDevice));
-    const size_t lds = ((size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2 + DN_PANEL_DOUBLES + 3 * SRBM_NUMAX + (SRBM_NUMAX + 1) / 2) * sizeof(double);
+    const size_t lds = DbgLds::END * sizeof(double);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_solve_mapped), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(srbm_k_debug_solve_mapped, dim3(count), dim3(DN_THREADS), lds, 0, n, nc, dmap, dM, dr, dx, dn);
     HIPCHK(hipGetLastError());
@@ -494,7 +491,7 @@ int srbm_debug_solve(int n, int count, const double* M_packed, const double* rhs
     HIPCHK(tmp.alloc(&dt, sizeof(int) * 2 * count));
     HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dr, rhs, vb, hipMemcpyHostToDevice));
-    const size_t lds = ((size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2 + DN_PANEL_DOUBLES + 2 * SRBM_NUMAX) * sizeof(double);
+    const size_t lds = DbgLds::XC * sizeof(double);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(srbm_k_debug_solve, dim3(count), dim3(DN_THREADS), lds, 0, n, dM, dr, dx, dX, dt);
     HIPCHK(hipGetLastError());
@@ -514,7 +511,7 @@ int srbm_debug_cholesky(int n, int count, const double* M_packed, double* L_pack
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dL, bytes)); HIPCHK(tmp.alloc(&dr, sizeof(int) * count));
     HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
-    const size_t lds = ((size_t)SRBM_NUMAX * (SRBM_NUMAX + 1) / 2 + DN_PANEL_DOUBLES) * sizeof(double);
+    const size_t lds = DbgLds::X * sizeof(double);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_cholesky), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(srbm_k_debug_cholesky, dim3(count), dim3(DN_THREADS), lds, 0, n, dM, dL, dr);
     HIPCHK(hipGetLastError());
@@ -574,23 +571,19 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     HIPCHK(hipMalloc(&h->d_time, sizeof(double) * B));
     HIPCHK(hipMalloc(&h->d_ee, sizeof(double) * 12 * B));
     // the IPM kernel gets the whole LDS of a CU: what its fixed map leaves over holds the dense state rows (K3Smem::sig_row)
-    h->k3_lds = K3_LDS_LAUNCH_BYTES;
-    if (srbm_k3_lds_bytes(h->hp.N) > h->k3_lds) return fail("srbm_batch_create: LDS map exceeds 160 KB");
-    h->hp.lds_doubles = (int)(h->k3_lds / sizeof(double));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k3_ipm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k3_ipm_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_rti_fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_rti_fused_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_rti_queued), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_rti_queued_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k3_normal_matrix), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->k3_lds));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_gait_sensitivity), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KG_DYN_LDS_BYTES));
-#ifdef SRBM_LARGE
-    static_assert(sizeof(K1Shared) <= 160 * 1024 && sizeof(K2Shared) <= 160 * 1024 && sizeof(K4Shared) <= 160 * 1024, "working sets fit the LDS of a CU");
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k1_assemble), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K1Shared)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k2_condense), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K2Shared)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k4_update), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K4Shared)));
-#endif
+    if (srbm_k3_lds_bytes(h->hp.N) > K3_LDS_LAUNCH_BYTES) return fail("srbm_batch_create: LDS map exceeds 160 KB");
+    h->hp.lds_doubles = (int)(K3_LDS_LAUNCH_BYTES / sizeof(double));
+    // the kernels launched with dynamic LDS beyond the default limit, with the constant their launches pass
+    const struct { const void* kernel; size_t lds; } dyn_lds[] = {
+        {reinterpret_cast<const void*>(srbm_k3_ipm), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_k3_ipm_long), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_fused), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_fused_long), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_queued), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_queued_long), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_k3_normal_matrix), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_k_gait_sensitivity), KG_DYN_LDS_BYTES}};
+    for (const auto& k : dyn_lds) HIPCHK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
     HIPCHK(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
     { const char* e = std::getenv("SRBM_NO_STEP_QUEUE"); h->queued_ok = !(e && e[0] == '1'); }
     h->params_dirty = true;
@@ -785,16 +778,16 @@ static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs
         if (!h->queues) HIPCHK(hipMalloc(&h->queues, sizeof(SrbmQueue) * SRBM_NQUEUES));
         hipLaunchKernelGGL(srbm_k_queue_init, dim3(SRBM_NQUEUES), dim3(256), 0, h->stream, h->queues, h->batch);
         if (h->hp.N <= K3_SHORT_N)
-            hipLaunchKernelGGL(srbm_rti_queued, dim3(h->n_cu), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, first_index, steps,
+            hipLaunchKernelGGL(srbm_rti_queued, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                                h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
         else
-            hipLaunchKernelGGL(srbm_rti_queued_long, dim3(h->n_cu), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, first_index, steps,
+            hipLaunchKernelGGL(srbm_rti_queued_long, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                                h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
     } else if (h->hp.N <= K3_SHORT_N)
-        hipLaunchKernelGGL(srbm_rti_fused, dim3(h->batch), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, first_index, steps,
+        hipLaunchKernelGGL(srbm_rti_fused, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                            h->d_state, h->d_time, h->d_ee, pl);
     else
-        hipLaunchKernelGGL(srbm_rti_fused_long, dim3(h->batch), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works, first_index, steps,
+        hipLaunchKernelGGL(srbm_rti_fused_long, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                            h->d_state, h->d_time, h->d_ee, pl);
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = steps; h->ev_used++; }
     HIPCHK(hipGetLastError());
@@ -1015,7 +1008,7 @@ int srbm_gait_compute_sensitivity(srbm_gait* g) {
                     "(srbm_gait_rti_advance does so by itself)");
     HIPCHK(hipSetDevice(h->device));
     if (upload_params(h)) return -1;
-    hipLaunchKernelGGL(srbm_k3_normal_matrix, dim3(h->batch), dim3(K3_THREADS), h->k3_lds, h->stream, h->dp, h->insts, h->works);
+    hipLaunchKernelGGL(srbm_k3_normal_matrix, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works);
     hipLaunchKernelGGL(srbm_k_gait_sensitivity, dim3(h->batch), dim3(KG_THREADS), KG_DYN_LDS_BYTES, h->stream, h->dp, h->insts, h->works, g->gw);
     HIPCHK(hipGetLastError());
     return 0;

@@ -8,7 +8,13 @@
 //                inequality sample tables, primal/dual iterates).
 // Everything is fp64 (the reference computes in Eigen::VectorXd) + int32 indices.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+/* The dynamic LDS of the workgroup, under the only name the library gives it.  The compiler treats two such declarations as two objects that
+   cannot alias, though both are the same bytes.  Every kernel lays its own views over it (K3Smem, the K1/K2/K4 working sets of the fused kernels
+   through srbm_lds_view, the offsets of the dense helpers); a change from one view to another is preceded by a workgroup barrier. */
+extern __shared__ double srbm_lds[];
 
 #define SRBM_NEE 4
 /* Where the packed normal matrix of the IPM lives: LDS (standard build: one workgroup of 512 threads per CU) or the work record in global

@@ -65,6 +65,19 @@ def test_product_never_touches_the_oracle():
                 assert 'oracle' not in txt.lower() or f == 'host.py' and 'oracle' not in txt, os.path.join(dirpath, f)
 
 
+def test_dynamic_lds_has_one_name():
+    """Two extern __shared__ arrays are two objects to the compiler, which assumes they do not alias though they are the same bytes:
+    the library declares one (srbm_lds, srbm_types.h), and kernels 1, 2, 4 use static LDS in every build."""
+    csrc = os.path.join(ROOT, 'bilevel-gait-gen_amd', 'csrc')
+    decls, dyn = [], []
+    for f in sorted(os.listdir(csrc)):
+        txt = open(os.path.join(csrc, f), errors='ignore').read()
+        decls += [f for _ in re.findall(r'\bextern\s+__shared__\b', txt)]
+        dyn += [f for _ in re.findall(r'\bSRBM_DYN_LDS\b', txt)]
+    assert decls == ['srbm_types.h'], decls
+    assert not dyn, dyn
+
+
 def test_manifold_tangent_helpers():
     q = np.array([0.0505, -0.1643, -0.0572, 0.9835]); q /= np.linalg.norm(q)
     s = np.concatenate([[0, 0, 0.3], [1, 2, 3], q, [0.1, 0.2, 0.3]])
