@@ -50,6 +50,8 @@ struct srbm_batch {
     int n_cu = 0;
     SrbmQueue* queues = nullptr;     // step queues of multi-step launches of a batch larger than the chip (srbm_fused.hiph), allocated at first use
     bool queued_ok = true;           // SRBM_NO_STEP_QUEUE=1 in the environment: such launches as one workgroup per instance (A/B, tests)
+    int last_launch_kernel = 0;      // kernel of the last srbm_rti_advance / srbm_closed_loop_advance with steps > 0 (srbm_debug_get_launch_info)
+    int last_launch_steps = 0;
     bool params_dirty = true;
     // optional HIP-event timing of the dominant kernel (srbm_k3_ipm) on the launch stream
     bool timing = false;
@@ -773,7 +775,9 @@ static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs
     const bool tm = h->timing && h->ev_used < h->ev_start.size();
     if (tm) HIPCHK(hipEventRecord(h->ev_start[h->ev_used], h->stream));
     // a batch larger than the chip, several steps: a resident grid takes (instance, step) items from the step queues (srbm_fused.hiph)
-    const bool queued = h->queued_ok && h->batch > h->n_cu && steps > 1 && steps < 65536 && h->batch <= SRBM_NQUEUES * (SRBM_QCAP - 1);
+    const bool queued = h->queued_ok && h->batch > h->n_cu && steps > 1 && steps <= SRBM_QUEUE_MAX_STEPS && h->batch <= SRBM_QUEUE_MAX_BATCH;
+    h->last_launch_kernel = (queued ? 3 : 1) + (h->hp.N <= K3_SHORT_N ? 0 : 1);
+    h->last_launch_steps = steps;
     if (queued) {
         if (!h->queues) HIPCHK(hipMalloc(&h->queues, sizeof(SrbmQueue) * SRBM_NQUEUES));
         hipLaunchKernelGGL(srbm_k_queue_init, dim3(SRBM_NQUEUES), dim3(256), 0, h->stream, h->queues, h->batch);
@@ -1237,6 +1241,14 @@ int srbm_debug_get_instance_iters(srbm_batch* h, double* iters /* [batch] */) {
     std::vector<SrbmInst> v;
     if (fetch_insts(h, v)) return -1;
     for (int b = 0; b < h->batch; b++) iters[b] = v[b].acc_iters;
+    return 0;
+}
+// which kernel the last srbm_rti_advance / srbm_closed_loop_advance with steps > 0 took (tests/test_gpu_launch_equivalence.py):
+// out4 = {CUs of the device, kernel (0 none yet, 1 srbm_rti_fused, 2 srbm_rti_fused_long, 3 srbm_rti_queued, 4 srbm_rti_queued_long), its steps,
+// 1 if that launch ran on the step queues}.  Host-side record of the choice made at launch; reads no device memory.
+int srbm_debug_get_launch_info(const srbm_batch* h, int* out4) {
+    if (!h || !out4) return fail("bad arguments");
+    out4[0] = h->n_cu; out4[1] = h->last_launch_kernel; out4[2] = h->last_launch_steps; out4[3] = h->last_launch_kernel >= 3 ? 1 : 0;
     return 0;
 }
 int srbm_get_work_counters(srbm_batch* h, double* total_ipm_iterations, double* total_algorithmic_flops) {

@@ -517,6 +517,12 @@ class BatchMPC:
         self._chk(self.L.srbm_get_kernel_timings(self.h, _d(ms), int(max_launches), C.byref(n)))
         return ms[:min(n.value, max_launches)].copy()
 
+    def debug_launch_info(self):
+        """srbm_debug_get_launch_info: the kernel the last srbm_rti_advance / srbm_closed_loop_advance with steps > 0 took (host-side record, no sync)"""
+        a = (C.c_int * 4)()
+        self._chk(self.L.srbm_debug_get_launch_info(self.h, a))
+        return dict(n_cu=a[0], kernel=(None, 'srbm_rti_fused', 'srbm_rti_fused_long', 'srbm_rti_queued', 'srbm_rti_queued_long')[a[1]], steps=a[2], queued=bool(a[3]))
+
     def work_counters(self):
         it = C.c_double(0); fl = C.c_double(0)
         self._chk(self.L.srbm_get_work_counters(self.h, C.byref(it), C.byref(fl)))

@@ -79,8 +79,9 @@ int srbm_set_solver_tolerances(srbm_batch* h, double tol_gap_abs, double tol_gap
  *     srbm_rti_advance_unfused, srbm_create_initial_run (one-step launches wait for the slowest instance every time), by
  *     srbm_closed_loop_advance (integration error and pushes make the attempts fail) and by srbm_gait_rti_advance (its candidates belong to
  *     other contact schedules).
- * SRBM_FAST_TOL_STEP / SRBM_FAST_START_MU are the values bench.py opts into for its headline line (1e-4 relative primal accuracy is the bar of
- * the path; parity of that mode: tests/test_gpu_resync.py); the same line carries the run at (0, 0). */
+ * bench.py's headline runs (0, SRBM_FAST_START_MU): the reference's termination criterion, every solve of srbm_rti_advance first attempted from
+ * the linearisation point.  Its named secondary object runs (SRBM_FAST_TOL_STEP, SRBM_FAST_START_MU) (1e-4 relative primal accuracy is the bar
+ * of the path), and the same line carries the run at (0, 0).  Parity of every mode: tests/test_gpu_resync.py, DESIGN.md sections 3-4. */
 #define SRBM_FAST_TOL_STEP 1e-5
 #define SRBM_FAST_START_MU 0.1
 int srbm_set_solver_step_rule(srbm_batch* h, double tol_step, double start_mu);
@@ -101,8 +102,9 @@ int srbm_get_real_time_update_dev(srbm_batch* h, const double* state_dev, const 
  * No host round trip between iterations.  Asynchronous; srbm_synchronize() to wait.
  * A batch of at most one instance per CU runs as one workgroup per instance for all steps; a LARGER batch with steps > 1 runs on a resident grid
  * that takes (instance, step) items from per-XCD queues (csrc/srbm_fused.hiph: the launch no longer ends with the instance whose `steps` solves
- * happen to be the longest) -- bitwise the same results (tests/test_gpu_queue.py); SRBM_NO_STEP_QUEUE=1 in the environment at srbm_create time
- * selects the first form for every batch.  The same holds for srbm_closed_loop_advance. */
+ * happen to be the longest) -- bitwise the same results (tests/test_gpu_queue.py), and bitwise those of the same steps launched one at a time
+ * (tests/test_gpu_launch_equivalence.py); launches of more than 32 767 steps and SRBM_NO_STEP_QUEUE=1 in the environment at srbm_create time
+ * select the first form.  The same holds for srbm_closed_loop_advance. */
 int srbm_rti_advance(srbm_batch* h, int first_index, int steps);
 /* same protocol with one kernel launch per phase and step (A/B measurements against the fused kernel) */
 int srbm_rti_advance_unfused(srbm_batch* h, int first_index, int steps);

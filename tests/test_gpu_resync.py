@@ -40,7 +40,7 @@ def make_batch(cfg, states, ees, step_rule=True, large=None):
     g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
     assert g.solver_step_rule() == (0.0, 0.0)   # a new batch: exactly the reference's criterion (gap 1e-15), include/srbm_rti.h
     if step_rule:
-        g.enable_fast_termination()             # the mode bench.py times: tol_step 1e-5, start_mu 0.1 (the latter acts in srbm_rti_advance only)
+        g.enable_fast_termination()             # bench.py's step_rule_mode: tol_step 1e-5, start_mu 0.1 (the latter acts in srbm_rti_advance only)
     oracles = []
     for b in range(B):
         o = OracleMPC(cfg)
@@ -49,12 +49,14 @@ def make_batch(cfg, states, ees, step_rule=True, large=None):
     return g, oracles
 
 
-def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=True, min_alive=None, fused=False, large=None, x_tol=REL_TOL, start_mu=None):
+def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=True, min_alive=None, fused=False, large=None, x_tol=REL_TOL, start_mu=None,
+                    qp_extra=()):
     """cold start on both sides, then `steps` open-loop RTI steps (test/gait_opt_playground.cpp:113-126) with the device
     re-synchronised to the oracle before every step; returns per-step statistics.  Asserts entry-wise parity.
     fused=False: the device steps through srbm_get_real_time_update (host-pointer entry, one launch per phase: the lower-start attempt is
     never made there).  fused=True: through srbm_rti_advance(i, 1) -- the device-resident launch bench.py times, which takes node 1 and the
-    spline feet of the installed trajectory as its inputs and, with start_mu > 0, begins every solve with the lower-start ATTEMPT."""
+    spline feet of the installed trajectory as its inputs and, with start_mu > 0, begins every solve with the lower-start ATTEMPT.
+    The assembled QP and the duals are compared at the steps i % qp_every == 0 and at the steps in qp_extra; primal and states at every step."""
     B = len(states)
     N = cfg['num_nodes']
     dt = cfg['integrator_dt']
@@ -113,6 +115,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
         x = g.qp_solution(); xr = g.raw_qp_minimiser(); z, s = g.dual_solution(); tr = g.trajectory_states()
         assert np.all(err[alive] == 0), (i, np.nonzero(err)[0][:8], err[err != 0][:8])
         traj_after = g.get_trajectory()
+        qp_step = i % qp_every == 0 or i in qp_extra
 
         def check(b):
             o = oracles[b]
@@ -152,7 +155,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
                 K = ko['K']
                 assert ta.nk[ee] == K, (i, b, ee)
                 assert np.array_equal(np.array(ta.knot_time[ee][:K]), ko['times']), (i, b, ee)
-            if i % qp_every == 0:
+            if qp_step:
                 A, bv, P, q = g.export_qp(b)
                 Ao, bo, Po, qo = o.qp_dense()
                 # sparsity pattern: identical above rounding noise.  (The reference's SetMatrix drops EXACT zeros,
@@ -181,7 +184,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
             assert out['states'] < x_tol, (i, b)
             # a sample is checked against the CERTIFIED minimiser of the QP (tests/qp_polish.py: active-set polish + KKT
             # certificate, independent of both interior-point codes): the oracle's minimiser is pinned by it, the device's too
-            if i % qp_every == 0 and (b + 5 * i) % 64 == 0:
+            if qp_step and (b + 5 * i) % 64 == 0:
                 from qp_polish import polish
                 is_eq = np.ones(m, bool)
                 is_eq[nx:nx + osz['n_ineq']] = False
@@ -195,7 +198,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
             # dual objectives agree.  Entry-wise z == z_oracle only where the multipliers are unique, i.e. where the gradients
             # of the active rows are linearly independent (a foot with zero force has its lower force-box row and its four
             # pyramid rows active together: five dependent rows, any split of the multiplier is optimal).
-            if i % qp_every == 0:
+            if qp_step:
                 zo, so_ = o.z(), o.s()
                 zg, sg = z[b, :m], s[b, :m]
                 xg = xr[b, :n]
@@ -292,9 +295,10 @@ def test_config_b_all_256_instances_entrywise_over_20_steps():
 
 
 def test_config_b_all_256_through_the_fused_launch_with_lower_start_attempts():
-    """THE MODE bench.py TIMES: all 256 Config-B instances over 20 steps through srbm_rti_advance(i, 1) with tol_step 1e-5 and
+    """bench.py's `step_rule_mode`: all 256 Config-B instances over 20 steps through srbm_rti_advance(i, 1) with tol_step 1e-5 and
     start_mu 0.1 -- every solve begins with the lower-start attempt, ends by the step rule or is repeated from the standard start -- entry-wise
-    against the oracle (Clarabel restatement at gap 1e-15) on identical QPs, same bounds as the host-pointer protocol above"""
+    against the oracle (Clarabel restatement at gap 1e-15) on identical QPs, same bounds as the host-pointer protocol above.  The headline mode,
+    (0, 0.1), has the same protocol below (test_config_b_reference_criterion_with_lower_start_through_the_fused_launch)"""
     cfg = load_config()
     B = 256
     states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
@@ -313,15 +317,29 @@ def test_config_b_all_256_through_the_fused_launch_with_lower_start_attempts():
     assert r['certified'] >= 40
 
 
-def test_config_d_share_through_the_fused_launch_with_lower_start_attempts():
-    """... the Config-D share (N = 50, dt = 0.02, pushed initial momenta; the 3-rows-per-thread instance of the kernel): 16 instances x 6 steps"""
+@pytest.mark.parametrize('tol_step', [1e-5, 0.0], ids=['step_rule', 'lower_start'])
+def test_config_d_share_through_the_fused_launch_with_lower_start_attempts(tol_step):
+    """... the Config-D share (N = 50, dt = 0.02, pushed initial momenta; the 3-rows-per-thread instance of the kernel): 64 instances x 12 steps in
+    both modes bench.py runs on Config D -- (1e-5, 0.1), and the headline (0, 0.1) with the strict dual bounds of the reference's criterion.
+    Which window sizes occur is decided by the oracle alone (its side of the protocol does not depend on the device): for these 64 instances
+    nx + 120 spline variables at steps 0-10, nx + 148 from step 11 on (a knot enters the window), touch-down rows from step 4 on, and no give-up
+    of the oracle's solver within the 12 steps.  The QPs and duals are compared at the even steps and at step 11, where the larger window first appears."""
     cfg = load_config('a1_config_distr_rejection')
-    B = 16
+    B = 64
     states, ees = zip(*[config_d_instance(cfg, b) for b in range(B)])
     states, ees = np.array(states), np.array(ees)
-    r = resync_protocol(cfg, states, ees, steps=6, qp_every=2, fused=True)
-    assert r['worst']['A'] <= 1e-12 and r['worst']['x'] < REL_TOL
-    print('resync parity through the fused launch, config D 16 x 6: alive', r['alive'], 'worst', r['worst'], r['counters'])
+    strict = tol_step == 0.0
+    r = resync_protocol(cfg, states, ees, steps=12, qp_every=2, qp_extra=(11,), fused=True, step_rule=not strict, start_mu=host.FAST_START_MU)
+    nx = 51 * 12
+    assert r['sizes'] == {nx + 120, nx + 148}, r['sizes']        # both window sizes were compared
+    assert r['td_steps'] > 0                                      # ... and steps with touch-down position rows
+    assert r['worst']['A'] <= 1e-12 and r['worst']['x'] < REL_TOL and r['worst']['states'] < REL_TOL
+    c = r['counters']
+    print('resync parity through the fused launch, config D 64 x 12, mode (%g, %g): alive' % (tol_step, host.FAST_START_MU), r['alive'], 'worst', r['worst'], c,
+          'device SolvedInacc at', r['inacc_where'], 'duals on the row space in %d solves' % r['duals_compared_on_row_space'])
+    assert c['low_tried'] == c['solves']
+    if strict:
+        assert r['worst']['z'] < REL_TOL and r['worst']['dual_obj'] <= 1e-6 and c['step_rule'] == 0, (r['worst'], c)
 
 
 def test_n40_share_through_the_fused_launch_with_lower_start_attempts():
@@ -337,19 +355,26 @@ def test_n40_share_through_the_fused_launch_with_lower_start_attempts():
 
 
 def test_config_b_reference_criterion_with_lower_start_through_the_fused_launch():
-    """srbm_set_solver_step_rule(0, 0.1): every solve ENDS by the reference's gap criterion, the fused launch first attempts it from the
-    linearisation point (the mode of bench.py's `reference_criterion_lower_start` object).  Same strict bounds as the (0, 0) run above -- dual
-    objective to 1e-6 of its value, stationarity 1e-7 -- on 128 instances x 12 steps, every solve began with an attempt"""
+    """srbm_set_solver_step_rule(0, 0.1) -- THE MODE OF bench.py's HEADLINE (`lower_start`): every solve ENDS by the reference's gap criterion, the
+    fused launch first attempts it from the linearisation point.  All 256 Config-B instances x 20 steps, the protocol and coverage of the other
+    256 x 20 runs (both window sizes, touch-down rows, certified minimisers) with the strict dual bounds of the (0, 0) run -- dual objective to
+    1e-6 of its value, stationarity 1e-7 --, every solve began with an attempt.  The oracle's own solver gives up on two of these instances
+    (98 and 115, MaxIterations at step 2: its side of the protocol does not depend on the device)."""
     cfg = load_config()
-    B = 128
+    B = 256
     states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
     states, ees = np.array(states), np.array(ees)
-    r = resync_protocol(cfg, states, ees, steps=12, step_rule=False, fused=True, start_mu=host.FAST_START_MU, min_alive=B - 3)
+    r = resync_protocol(cfg, states, ees, steps=20, step_rule=False, fused=True, start_mu=host.FAST_START_MU, min_alive=B - 2)
     c = r['counters']
-    print('resync parity, reference criterion + lower start through the fused launch, 128 x 12: worst', r['worst'], c, 'device SolvedInacc at', r['inacc_where'],
-          'duals on the row space in %d solves' % r['duals_compared_on_row_space'])
+    print('resync parity, reference criterion + lower start through the fused launch, 256 x 20: alive', r['alive'], 'worst', r['worst'], c,
+          'device SolvedInacc at', r['inacc_where'], 'duals on the row space in %d solves' % r['duals_compared_on_row_space'], 'certified minimisers: %d' % r['certified'],
+          'oracle gave up on %d solves, device certified there: %d' % (r['oracle_gave_up'], r['device_certified_where_oracle_gave_up']))
+    nx = 21 * 12
+    assert {nx + 120, nx + 148} <= r['sizes'], r['sizes']         # both window sizes were compared
+    assert r['td_steps'] > 0                                      # ... and steps with touch-down position rows
     assert r['worst']['A'] <= 1e-12 and r['worst']['x'] < REL_TOL and r['worst']['z'] < REL_TOL and r['worst']['dual_obj'] <= 1e-6
     assert c['step_rule'] == 0 and c['low_tried'] == c['solves'] and c["low_failed"] <= 0.4 * c["solves"], c
+    assert r['certified'] >= 40
 
 
 def test_config_b_reference_criterion_through_the_fused_launch():
