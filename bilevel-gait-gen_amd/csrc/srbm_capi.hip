@@ -17,6 +17,8 @@
 #include "srbm_fused.hiph"
 #include "srbm_ik.hiph"
 #include "srbm_wbc.hiph"
+#include "srbm_batch.hiph"
+#include "srbm_dense_hooks.hiph"
 #include "../../include/srbm_rti.h"
 
 static thread_local std::string g_err;
@@ -89,229 +91,52 @@ static int batch_stage(srbm_batch* h, size_t bytes, void** dev, void** host) {
     *host = h->h_stage;
     return 0;
 }
-
-__global__ void srbm_k_pack_results(const SrbmParams* __restrict__ Pp, const SrbmInst* __restrict__ insts, const SrbmWork* __restrict__ works,
-                                    double* __restrict__ out, int ld) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const SrbmInst& I = insts[b];
-    const int N = Pp->N, NX = 12 * (N + 1) + SRBM_NUMAX, NM = 12 * (N + 1) + 6 * SRBM_NSMAX + 16 * (N - 3) + 16;
-    double* o = out + (size_t)b * ld;
-    if (tid == 0) { o[0] = I.status; o[1] = I.n; o[2] = I.m; o[3] = I.cost; o[4] = I.alpha; o[5] = I.err_acc | I.err; o[6] = I.qp_iters; o[7] = I.init_time; }
-    for (int i = tid; i < NX && 8 + i < ld; i += blockDim.x) o[8 + i] = i < I.n ? works[b].x[i] : 0.0;
-    for (int i = tid; i < NM && 8 + NX + i < ld; i += blockDim.x) o[8 + NX + i] = i < I.m ? works[b].z[i] : 0.0;
-    // contact times (Trajectory::GetContactTimes): counts of the four feet, then 8 slots per foot
-    const int oc = 8 + NX + NM;
-    if (tid < SRBM_NEE && oc + 4 + 8 * SRBM_NEE <= ld) {
-        int n = 0;
-        for (int i = 0; i < I.nk[tid]; i++)
-            if (I.kind[tid][i] <= SRBM_K_TD) { if (n < 8) o[oc + 4 + 8 * tid + n] = I.knot_t[tid][i]; n++; }
-        o[oc + tid] = n;
-        for (int i = n; i < 8; i++) o[oc + 4 + 8 * tid + i] = 0.0;
-    }
-}
-
-// Trajectory::GetForce / GetEndEffectorLocation / GetContacts of the current trajectory at time[b] (trajectory.cpp:395-410, :70-80)
-__global__ void srbm_k_eval_trajectory(const SrbmParams* __restrict__ Pp, SrbmInst* __restrict__ insts, const double* __restrict__ time,
-                                       double* __restrict__ force, double* __restrict__ pos, int* __restrict__ in_contact) {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= Pp->batch * SRBM_NEE) return;
-    const int b = w / SRBM_NEE, ee = w % SRBM_NEE;
-    SrbmInst& I = insts[b];
-    const FootView f{I.knot_t[ee], I.kind[ee], I.nk[ee]};
-    int err = 0;
-    const double t = time[b];
-    double F[3], xy[2];
-    srbm_force_value(f, &I.fval[ee][0][0][0], t, F, &err);
-    srbm_posxy_value(f, &I.pval[ee][0][0], t, xy, &err);
-    const double z = srbm_posz_value(f, t, Pp->swing_height, Pp->foot_offset, &err);
-    const int lo = srbm_lower(f, SEL_POSXY, t, &err), up = srbm_upper(f, SEL_POSXY, t, &err);
-    for (int c = 0; c < 3; c++) force[(size_t)w * 3 + c] = F[c];
-    pos[(size_t)w * 3] = xy[0]; pos[(size_t)w * 3 + 1] = xy[1]; pos[(size_t)w * 3 + 2] = z;
-    in_contact[w] = (f.kind[lo] == SRBM_K_TD && f.kind[up] == SRBM_K_LO) ? 1 : 0;      // EndEffectorSplines::IsInContact (:805-813)
-    if (err) atomicOr(&I.err, err);
-}
-
-// ---------------- small device kernels of the host protocol ----------------
-
-// default contact schedule [0,.3,.6,.9,1.2] per foot (mpc.cpp:566-608), FR and RL start in stance (trajectory.cpp:25-28),
-// three force polynomials per stance (end_effector_splines.cpp:34-153)
-__global__ void srbm_k_init(const SrbmParams* __restrict__ Pp, SrbmInst* __restrict__ insts) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= Pp->batch) return;
-    SrbmInst& I = insts[b];
-    const double times[5] = {0, 0.3, 0.6, 0.9, 1.2};
-    for (int ee = 0; ee < SRBM_NEE; ee++) {
-        const bool start_in_contact = (ee == 1 || ee == 2);
-        // pattern of 5 knot kinds, repeated until all contact times are placed
-        const uint8_t pat_sw[5] = {SRBM_K_LO, SRBM_K_MID, SRBM_K_TD, SRBM_K_F, SRBM_K_F};
-        const uint8_t pat_st[5] = {SRBM_K_TD, SRBM_K_F, SRBM_K_F, SRBM_K_LO, SRBM_K_MID};
-        int i = 0, j = 0, k = 1, nk = 0;
-        while (i < 5) {
-            const uint8_t kd = start_in_contact ? pat_st[j % 5] : pat_sw[j % 5];
-            double t;
-            if (kd == SRBM_K_F) {
-                const double d = times[i] - times[i - 1];
-                const double kdv = k * d;
-                const double q = kdv / 3;
-                t = times[i - 1] + q;
-                k++;
-            } else if (kd == SRBM_K_MID) {
-                const double d = times[i] - times[i - 1];
-                const double hlf = d / 2;
-                t = times[i - 1] + hlf;
-            } else {
-                t = times[i];
-                i++; k = 1;
-            }
-            I.knot_t[ee][nk] = t; I.kind[ee][nk] = kd;
-            nk++; j++;
-        }
-        I.nk[ee] = nk;
-        for (int q = nk; q < SRBM_KMAX; q++) { I.knot_t[ee][q] = 0; I.kind[ee][q] = 0; }
-        for (int c = 0; c < 3; c++) for (int q = 0; q < SRBM_KMAX; q++) { I.fval[ee][c][q][0] = 0; I.fval[ee][c][q][1] = 0; }
-        for (int c = 0; c < 2; c++) for (int q = 0; q < SRBM_KMAX; q++) I.pval[ee][c][q] = 0;
-    }
-    for (int i = 0; i < (SRBM_NMAX + 1) * 13; i++) I.states[i] = 0;
-    I.box[0] = Pp->box0[0]; I.box[1] = Pp->box0[1];
-    I.init_time = 0; I.alpha = 0; I.cost = 0; I.eq_violation = 0; I.step_norm = 0; I.qp_cost = 0; I.res_primal = 0; I.res_dual = 0; I.gap = 0;
-    I.status = SRBM_UNSOLVED; I.qp_iters = 0; I.n = 0; I.m = 0; I.n_eq = 0; I.n_ineq = 0; I.nfv = 0; I.npv = 0; I.n_td = 0; I.n_samples = 0;
-    I.err = 0; I.run_num = 0; I.acc_iters = 0; I.acc_flops = 0;
-    I.cost_sum = 0; I.merit_dd = 0; I.acc_mfma = 0; I.err_acc = 0; I.n_solves = 0; I.n_not_solved = 0; I.n_maxiter = 0;
-    I.low_streak = 0; I.last_rule = 0; I.last_low = 0; I.pad_low = 0; I.low_skip = 0; I.n_low_tried = 0; I.n_low_failed = 0; I.n_step_rule = 0;
-}
-
-__global__ void srbm_k_warm_start(const SrbmParams* __restrict__ Pp, SrbmInst* __restrict__ insts, const double* __restrict__ states) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < (Pp->N + 1) * 13; i += blockDim.x) insts[b].states[i] = states[(size_t)b * 13 + (i % 13)];
-}
-
-// EndEffectorSplines::SetContactTimes (end_effector_splines.cpp:860-892) for every foot of every instance
-__global__ void srbm_k_set_contact_times(const SrbmParams* __restrict__ Pp, SrbmInst* __restrict__ insts, const double* __restrict__ times, int ld) {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= Pp->batch * SRBM_NEE) return;
-    const int b = w / SRBM_NEE, ee = w % SRBM_NEE;
-    SrbmInst& I = insts[b];
-    srbm_apply_contact_times(I, ee, times + ((size_t)b * SRBM_NEE + ee) * ld, srbm_num_contacts(I, ee));
-}
-
-// ---------------- trajectory -> whole-body targets (srbm_ik.hiph) ----------------
-__device__ __forceinline__ const SrbmLegs& srbm_legs(const SrbmParams& P) { return *reinterpret_cast<const SrbmLegs*>(&P.legs[0][0][0]); }
-__global__ void srbm_k_forward_kinematics(const SrbmParams* __restrict__ Pp, const double* __restrict__ q, double* __restrict__ ee) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= Pp->batch) return;
-    ik_forward_kinematics(srbm_legs(*Pp), q + (size_t)b * 19, ee + (size_t)b * 12);
-}
-// One wave per instance (srbm_ik.hiph): every lane runs the same chain on the same data, the small vectors live in LDS, lane 0 stores.
-#define SRBM_IK_THREADS 64
-__global__ __launch_bounds__(SRBM_IK_THREADS) void srbm_k_inverse_kinematics(const SrbmParams* __restrict__ Pp, const double* __restrict__ state, const double* __restrict__ ee,
-                                          const double* __restrict__ q_guess, double* __restrict__ q_out, int* __restrict__ iters, int* __restrict__ status) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    __shared__ double q[19], s13[13], e12[12];
-    __shared__ int it[4];
-    if (lane < 19) q[lane] = q_guess[(size_t)b * 19 + lane];
-    if (lane < 13) s13[lane] = state[(size_t)b * 13 + lane];
-    if (lane < 12) e12[lane] = ee[(size_t)b * 12 + lane];
-    __syncthreads();
-    const int failed = ik_inverse_kinematics(srbm_legs(*Pp), s13, e12, q, it);
-    __syncthreads();
-    if (lane < 19) q_out[(size_t)b * 19 + lane] = q[lane];
-    if (lane < 4) iters[b * 4 + lane] = it[lane];
-    if (lane == 0) status[b] = failed;
-}
-// MPCController::GetTargetsFromTraj: two IK solves per instance -- the targets at `time`, then at time + dt from the first solve's joint angles.
-// TWO WAVES per instance.  Inside a solve the feet are strictly one after the other (they share the base pose), and the second solve takes from the first
-// only the joint angles of a leg as the guess of that leg's foot -- final as soon as the first solve has finished THAT foot.  So wave 1 runs the second
-// solve one foot behind wave 0: five foot slots instead of eight, each wave the same chain of operations on the same data as before (bitwise the same
-// results), on its own SIMD of the CU.
-#define SRBM_TT_THREADS (2 * SRBM_IK_THREADS)
-__global__ __launch_bounds__(SRBM_TT_THREADS) void srbm_k_targets_from_traj(const SrbmParams* __restrict__ Pp, const SrbmInst* __restrict__ insts, const double* __restrict__ time_in,
-                                         double* __restrict__ q_des, double* __restrict__ v_des, double* __restrict__ force_des, int* __restrict__ status) {
-    const int b = blockIdx.x, lane = threadIdx.x, wv = threadIdx.x / SRBM_IK_THREADS;
-    const SrbmParams& P = *Pp;
-    const SrbmInst& I = insts[b];
-    const int N = P.N;
-    const double t0 = I.init_time, dt = P.dt;
-    double time = time_in[b];
-    if (time < t0) time = t0;
-    const int node = (int)ceil((time - t0) / dt);
-    if (node < 0 || node + 1 > N) { if (lane == 0) status[b] = 2; return; }          // GetState(node + 1) beyond the horizon: the reference's vector access throws
-    __shared__ double s1[13], s2[13], ee1[12], ee2[12], F[12], q[19], q2[19];
-    __shared__ int flags[2], ik_failed[2];
-    auto T = [&](int k) { return t0 + dt * k; };
-    const double* S = I.states;
-    if (lane < 2) flags[lane] = 0;
-    __syncthreads();
-    if (lane < 13) {
-        const int i = lane;
-        if (node > 0) {
-            const double a = 1 - (T(node) - time) / (T(node) - T(node - 1));
-            s1[i] = (S[node * 13 + i] - S[(node - 1) * 13 + i]) * a + S[(node - 1) * 13 + i];
-            const double c = 1 - (T(node + 1) - (time + dt)) / (T(node + 1) - T(node));
-            s2[i] = (S[(node + 1) * 13 + i] - S[node * 13 + i]) * c + S[node * 13 + i];
-        } else {
-            const double a = 1 - (T(1) - time) / (T(1) - T(0));
-            const double c = 1 - (T(1) - (time + dt)) / (T(1) - T(0));
-            s1[i] = (S[13 + i] - S[i]) * a + S[i]; s2[i] = (S[13 + i] - S[i]) * c + S[i];
-        }
-    }
-    if (lane >= 16 && lane < 16 + SRBM_NEE) {        // the splines of one foot per lane
-        const int ee = lane - 16;
-        int err = 0;
-        const FootView f{I.knot_t[ee], I.kind[ee], I.nk[ee]};
-        double e1[3], e2[3], ff[3];
-        srbm_posxy_value(f, &I.pval[ee][0][0], time, e1, &err);
-        e1[2] = srbm_posz_value(f, time, P.swing_height, P.foot_offset, &err);
-        srbm_posxy_value(f, &I.pval[ee][0][0], time + dt, e2, &err);
-        e2[2] = srbm_posz_value(f, time + dt, P.swing_height, P.foot_offset, &err);
-        srbm_force_value(f, &I.fval[ee][0][0][0], time, ff, &err);
-        for (int c = 0; c < 3; c++) { ee1[3 * ee + c] = e1[c]; ee2[3 * ee + c] = e2[c]; F[3 * ee + c] = ff[c]; }
-        if (err) atomicOr(&flags[0], 1);
-    }
-    if (lane >= 32 && lane < 32 + 19) q[lane - 32] = q_des[(size_t)b * 19 + lane - 32];
-    __syncthreads();
-    int st = 0;
-    if (node > 0 && time + dt < T(node)) st = 2;                              // "bad interp."
-    if (flags[0]) st = 2;
-    const SrbmLegs& L = srbm_legs(P);
-    {
-        // SingleRigidBodyModel::InverseKinematics (ik_inverse_kinematics, srbm_ik.hiph) of this wave's solve, foot by foot in step with the other wave
-        const double* st13 = wv ? s2 : s1;
-        const double* eed = wv ? ee2 : ee1;
-        double* qo = wv ? q2 : q;
-        const IkR Rdes = ik_quat_to_R(st13 + 6);
-        const Ik3 pdes = {st13[0], st13[1], st13[2]};
-        double p[3] = {st13[0], st13[1], st13[2]}, qt[4] = {st13[6], st13[7], st13[8], st13[9]};
-        int failed = 0;
-        bool any_success = false;
-        #pragma unroll 1
-        for (int slot = 0; slot < SRBM_NEE + 1; slot++) {
-            const int ee = slot - wv;
-            if (ee >= 0 && ee < SRBM_NEE) {
-                const Ik3 edes = {eed[3 * ee], eed[3 * ee + 1], eed[3 * ee + 2]};
-                double ang[3] = {q[7 + 3 * ee], q[8 + 3 * ee], q[9 + 3 * ee]};        // wave 0: the guess handed in; wave 1: wave 0's result of the slot before
-                bool success;
-                ik_solve_foot(&L.origin[ee][0][0], Rdes, pdes, edes, p, qt, ang, &success);
-                qo[7 + 3 * ee] = ang[0]; qo[8 + 3 * ee] = ang[1]; qo[9 + 3 * ee] = ang[2];
-                any_success = any_success || success;
-                if (!any_success) failed = 1;
-            }
-            __syncthreads();
-        }
-        qo[0] = p[0]; qo[1] = p[1]; qo[2] = p[2]; qo[3] = qt[0]; qo[4] = qt[1]; qo[5] = qt[2]; qo[6] = qt[3];
-        if ((lane & (SRBM_IK_THREADS - 1)) == 0) ik_failed[wv] = failed;
-    }
-    __syncthreads();
-    if ((ik_failed[0] || ik_failed[1]) && st == 0) st = 1;
-    double* v = v_des + (size_t)b * 18;
-    if (lane < 3) v[lane] = s1[3 + lane] / P.mass;
-    else if (lane < 6) { const int i = lane - 3; v[lane] = P.Ir_inv[3 * i] * s1[10] + P.Ir_inv[3 * i + 1] * s1[11] + P.Ir_inv[3 * i + 2] * s1[12]; }
-    else if (lane < 18) { const int j = lane - 6; v[lane] = (-q[7 + j] + q2[7 + j]) / dt; }
-    if (lane < 19) q_des[(size_t)b * 19 + lane] = q[lane];
-    if (lane < 12) force_des[(size_t)b * 12 + lane] = F[lane];
-    if (lane == 0) status[b] = st;
-}
+// The layout of a staging buffer: sub-buffers handed out in order, each at an 8-byte boundary, at the same offset in the device scratch and in
+// its pinned host mirror.  add() lays the parts out, stage() / scratch() take the buffer (batch_stage / batch_scratch), dev() / host() place them.
+template <class T> struct Part { size_t off, n; size_t bytes() const { return sizeof(T) * n; } };
+struct Carve {
+    size_t end = 0;
+    char *d = nullptr, *hm = nullptr;
+    template <class T> Part<T> add(size_t n) { const size_t off = (end + 7) / 8 * 8; end = off + sizeof(T) * n; return {off, n}; }
+    int stage(srbm_batch* h) { void *dv, *hv; if (batch_stage(h, end, &dv, &hv)) return -1; d = static_cast<char*>(dv); hm = static_cast<char*>(hv); return 0; }
+    int scratch(srbm_batch* h) { void* dv; if (batch_scratch(h, end, &dv)) return -1; d = static_cast<char*>(dv); return 0; }
+    template <class T> T* dev(Part<T> p) const { return reinterpret_cast<T*>(d + p.off); }
+    template <class T> T* host(Part<T> p) const { return reinterpret_cast<T*>(hm + p.off); }
+    template <class A, class B> static size_t span(Part<A> first, Part<B> last) { return last.off + last.bytes() - first.off; }   // bytes first..last
+};
 
 // ---------------- host helpers ----------------
+struct Copy { void* dst; const void* src; size_t bytes; };        // one hipMemcpy; dst == nullptr: an optional output that was not asked for
+static int copy_each(std::initializer_list<Copy> cs, hipMemcpyKind kind) {
+    for (const Copy& c : cs) if (c.dst) HIPCHK(hipMemcpy(c.dst, c.src, c.bytes, kind));
+    return 0;
+}
+// device -> host copies, after the work queued on the batch's stream
+static int fetch(srbm_batch* h, std::initializer_list<Copy> cs) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return copy_each(cs, hipMemcpyDeviceToHost);
+}
+// the field at `offset` of instance `inst`'s SrbmWork (device address)
+static const void* work_field(const srbm_batch* h, int inst, size_t offset) { return reinterpret_cast<const char*>(h->works + inst) + offset; }
+// one SrbmWork field of every instance, `count` doubles of it per row of `out`
+static int fetch_work_field(srbm_batch* h, size_t offset, size_t count, double* out, int ld) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((size_t)ld < count) return fail("leading dimension too small");
+    HIPCHK(hipMemcpy2D(out, sizeof(double) * ld, reinterpret_cast<const char*>(h->works) + offset, sizeof(SrbmWork), sizeof(double) * count,
+                       h->batch, hipMemcpyDeviceToHost));
+    return 0;
+}
+// the SrbmInst array on the host, after the work queued on the batch's stream: f(b, instance b) for every instance
+template <class F> static int each_inst(srbm_batch* h, F f) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<SrbmInst> v(h->batch);
+    HIPCHK(hipMemcpy(v.data(), h->insts, sizeof(SrbmInst) * (size_t)h->batch, hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->batch; b++) f(b, v[b]);
+    return 0;
+}
 static int upload_params(srbm_batch* h) {
     if (!h->params_dirty) return 0;
     h->hp.q_diag = 1;
@@ -327,10 +152,15 @@ static void inv3(const double* m, double* r) {
     r[3] = (f * g - d * i) / det; r[4] = (a * i - c * g) / det; r[5] = (c * d - a * f) / det;
     r[6] = (d * hh - e * g) / det; r[7] = (b * g - a * hh) / det; r[8] = (a * e - b * d) / det;
 }
-// one RTI step as four launches.  exact: the solve is taken to the gap criterion whatever the batch's step rule says (the solve whose KKT
-// sensitivity the gait step differentiates)
-// One RTI step on inputs already in h->d_state / d_time / d_ee: four kernels.  exact: to the gap criterion whatever the batch's step rule says (the solve a gait
-// gradient differentiates).
+// the batch's device made current, its parameters uploaded if they changed: the start of every entry that launches
+static int use_batch(srbm_batch* h) {
+    HIPCHK(hipSetDevice(h->device));
+    return upload_params(h);
+}
+// the IPM variant of every launch path: the _long kernels beyond K3_SHORT_N nodes (srbm_k3_ipm.hiph)
+static bool k3_long(const srbm_batch* h) { return h->hp.N > K3_SHORT_N; }
+// One RTI step on inputs already in h->d_state / d_time / d_ee: four kernels.  exact: the solve is taken to the gap criterion whatever the batch's
+// step rule says (the solve whose KKT sensitivity the gait step differentiates).
 // (Measured in round 5: the same step as ONE launch of the fused kernel -- no grid-wide wait between the phases, a workgroup through with its line-search
 //  candidate takes the next one -- is SLOWER: gait segment 7.06 -> 7.34 ms per step; the stand-alone IPM kernel is an entry function -- its uniform
 //  loads are scalar, it spills less (scratch 396 B per lane against 988) -- and that outweighs three kernel tails.)
@@ -347,116 +177,38 @@ static int launch_step(srbm_batch* h, bool exact = false) {
     hipLaunchKernelGGL(srbm_k2_condense, dim3(B), dim3(K2_THREADS), 0, h->stream, h->dp, h->insts, h->works);
     const bool tm = h->timing && h->ev_used < h->ev_start.size();
     if (tm) HIPCHK(hipEventRecord(h->ev_start[h->ev_used], h->stream));
-    if (h->hp.N <= K3_SHORT_N) hipLaunchKernelGGL(srbm_k3_ipm, dim3(B), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
-    else hipLaunchKernelGGL(srbm_k3_ipm_long, dim3(B), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
+    const auto k3 = k3_long(h) ? srbm_k3_ipm_long : srbm_k3_ipm;
+    hipLaunchKernelGGL(k3, dim3(B), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, tol_step, start_mu);
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = 1; h->ev_used++; }
     hipLaunchKernelGGL(srbm_k4_update, dim3(B), dim3(K4_THREADS), 0, h->stream, h->dp, h->insts, h->works);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
+// The unit-test hooks of the dense blocks (srbm_dense_hooks.hiph): inputs in, the kernel on `count` workgroups with `lds` bytes of dynamic LDS,
+// a device-wide wait, outputs back
+template <class... P, class... A>
+static int run_dense_hook(void (*kernel)(P...), int count, size_t lds, std::initializer_list<Copy> in, std::initializer_list<Copy> out, A... args) {
+    if (copy_each(in, hipMemcpyHostToDevice)) return -1;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(count), dim3(DN_THREADS), lds, 0, args...);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    return copy_each(out, hipMemcpyDeviceToHost);
+}
+
 extern "C" {
 
-static int fetch_insts(srbm_batch* h, std::vector<SrbmInst>& v);
 const char* srbm_last_error(void) { return g_err.c_str(); }
 long srbm_bytes_per_instance(void) { return (long)(sizeof(SrbmInst) + sizeof(SrbmWork)); }
 /* diagnostic builds (-DSRBM_PROFILE) only: cycles per IPM phase of one instance, 16 slots */
 int srbm_debug_get_profile(srbm_batch* h, int inst, double* out16) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out16, reinterpret_cast<const char*>(h->works + inst) + offsetof(SrbmWork, prof), sizeof(double) * 16, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(h, {{out16, work_field(h, inst, offsetof(SrbmWork, prof)), sizeof(double) * 16}});
 }
 int srbm_debug_get_profile2(srbm_batch* h, int inst, double* out96) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out96, reinterpret_cast<const char*>(h->works + inst) + offsetof(SrbmWork, prof2), sizeof(double) * 96, hipMemcpyDeviceToHost));
-    return 0;
-}
-// LDS map of the unit-test hooks of the dense building blocks (doubles into srbm_lds): the packed matrix, the Cholesky panel, x, t, xc, the int
-// column map.  Each hook is launched with the LDS up to the end of the last array it uses.  The map starts 16 doubles in: with the matrix and
-// the panel where the IPM has them (K3Smem: 0 and SRBM_HPACK), every call of the dense helpers would pass the same LDS addresses, the compiler
-// propagates them into the helpers as constants, and the IPM's factorisation gets slower (Cholesky +4 % of its ticks; docs/history.md).
-struct DbgLds {
-    static constexpr int M = 16, PANEL = M + SRBM_HPACK, X = PANEL + DN_PANEL_DOUBLES, T = X + SRBM_NUMAX, XC = T + SRBM_NUMAX, MAP = XC + SRBM_NUMAX,
-                         END = MAP + (SRBM_NUMAX + 1) / 2;
-};
-// unit-test hook for the dense building blocks: Cholesky of `count` packed lower-triangular n x n matrices, one workgroup each
-__global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve(int n, const double* __restrict__ Min, const double* __restrict__ rhs,
-                                                               double* __restrict__ xout, double* __restrict__ Xout, int* __restrict__ ticks) {
-    const int np = n * (n + 1) / 2;
-    double* M = srbm_lds + DbgLds::M;
-    double* panel = srbm_lds + DbgLds::PANEL;
-    double* xv = srbm_lds + DbgLds::X;
-    double* tv = srbm_lds + DbgLds::T;
-    const double* src = Min + (size_t)blockIdx.x * np;
-    for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
-    for (int e = threadIdx.x; e < n; e += DN_THREADS) xv[e] = rhs[(size_t)blockIdx.x * n + e];
-    __syncthreads();
-    DnTiles T;
-    int nreg = 0;
-    dn_load_packed(T, M, n);
-    dn_cholesky(T, M, n, panel, &nreg);
-    chol_invert_diag_blocks(M, n, panel);
-    const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-    dn_trtri(M, n, panel);
-    const long long t1 = (long long)__builtin_amdgcn_s_memtime();
-    dn_solve_inv(DbgLds::M, n, DbgLds::X, DbgLds::T, -1, 0, 0
-#ifdef SRBM_M_GLOBAL
-                 , M
-#endif
-    );
-    const long long t2 = (long long)__builtin_amdgcn_s_memtime();
-    for (int e = threadIdx.x; e < n; e += DN_THREADS) xout[(size_t)blockIdx.x * n + e] = xv[e];
-    for (int e = threadIdx.x; e < np; e += DN_THREADS) Xout[(size_t)blockIdx.x * np + e] = M[e];
-    if (threadIdx.x == 0) { ticks[2 * blockIdx.x] = (int)(t1 - t0); ticks[2 * blockIdx.x + 1] = (int)(t2 - t1); }
-}
-__global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_cholesky(int n, const double* __restrict__ Min, double* __restrict__ Lout, int* __restrict__ nreg_out) {
-    const int np = n * (n + 1) / 2;
-    double* M = srbm_lds + DbgLds::M;
-    double* panel = srbm_lds + DbgLds::PANEL;
-    const double* src = Min + (size_t)blockIdx.x * np;
-    for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
-    __syncthreads();
-    DnTiles T;
-    int nreg = 0;
-    const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-    dn_load_packed(T, M, n);
-    dn_cholesky(T, M, n, panel, &nreg);
-    const long long t1 = (long long)__builtin_amdgcn_s_memtime();
-    dn_scale_factor_columns(M, n, panel);         // (the test looks at L; dn_cholesky leaves L diag(sqrt(d)))
-    for (int e = threadIdx.x; e < np; e += DN_THREADS) Lout[(size_t)blockIdx.x * np + e] = M[e];
-    if (threadIdx.x == 0) nreg_out[blockIdx.x] = nreg | ((int)min((long long)0x7fffff, (t1 - t0) >> 4) << 8);   // bits 8..: ticks / 16 (diagnostic)
-}
-// unit-test hook for the dense phase on a subset of the columns (what the IPM does with the pinned position variables): tiles loaded through
-// the column map, factor + inverse of the mapped block, solve with the gather / scatter through the map; unmapped entries of x keep rhs
-__global__ __launch_bounds__(DN_THREADS) void srbm_k_debug_solve_mapped(int n, int nc, const int* __restrict__ map, const double* __restrict__ Min,
-                                                                      const double* __restrict__ rhs, double* __restrict__ xout, int* __restrict__ nreg_out) {
-    const int np = n * (n + 1) / 2;
-    double* M = srbm_lds + DbgLds::M;
-    double* panel = srbm_lds + DbgLds::PANEL;
-    double* xv = srbm_lds + DbgLds::X;
-    int* imap = reinterpret_cast<int*>(srbm_lds + DbgLds::MAP);
-    const double* src = Min + (size_t)blockIdx.x * np;
-    for (int e = threadIdx.x; e < np; e += DN_THREADS) M[e] = src[e];
-    for (int e = threadIdx.x; e < n; e += DN_THREADS) xv[e] = rhs[(size_t)blockIdx.x * n + e];
-    for (int e = threadIdx.x; e < nc; e += DN_THREADS) imap[e] = map[e];
-    __syncthreads();
-    DnTiles T;
-    int nreg = 0;
-    dn_load_packed(T, M, nc, imap);
-    dn_cholesky(T, M, nc, panel, &nreg);
-    chol_invert_diag_blocks(M, nc, panel);
-    dn_trtri(M, nc, panel);
-    dn_solve_inv(DbgLds::M, nc, DbgLds::X, DbgLds::T, DbgLds::MAP, DbgLds::XC, 0
-#ifdef SRBM_M_GLOBAL
-                 , M
-#endif
-    );
-    for (int e = threadIdx.x; e < n; e += DN_THREADS) xout[(size_t)blockIdx.x * n + e] = xv[e];
-    if (threadIdx.x == 0) nreg_out[blockIdx.x] = nreg;
+    return fetch(h, {{out96, work_field(h, inst, offsetof(SrbmWork, prof2)), sizeof(double) * 96}});
 }
 int srbm_debug_solve_mapped(int n, int nc, const int* map, int count, const double* M_packed, const double* rhs, double* x, int* nreg) {
 #ifdef SRBM_LARGE
@@ -468,17 +220,8 @@ int srbm_debug_solve_mapped(int n, int nc, const int* map, int count, const doub
     double *dM = nullptr, *dr = nullptr, *dx = nullptr; int *dmap = nullptr, *dn = nullptr;
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dr, vb)); HIPCHK(tmp.alloc(&dx, vb)); HIPCHK(tmp.alloc(&dmap, sizeof(int) * nc)); HIPCHK(tmp.alloc(&dn, sizeof(int) * count));
-    HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dr, rhs, vb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dmap, map, sizeof(int) * nc, hipMemcpyHostToDevice));
-    const size_t lds = DbgLds::END * sizeof(double);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_solve_mapped), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(srbm_k_debug_solve_mapped, dim3(count), dim3(DN_THREADS), lds, 0, n, nc, dmap, dM, dr, dx, dn);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(x, dx, vb, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(nreg, dn, sizeof(int) * count, hipMemcpyDeviceToHost));
-    return 0;
+    return run_dense_hook(srbm_k_debug_solve_mapped, count, DbgLds::END * sizeof(double), {{dM, M_packed, bytes}, {dr, rhs, vb}, {dmap, map, sizeof(int) * nc}},
+                          {{x, dx, vb}, {nreg, dn, sizeof(int) * count}}, n, nc, dmap, dM, dr, dx, dn);
 }
 /* unit-test hook: x = M^-1 rhs through Cholesky + explicit inverse of the factor; X_packed = L^-1; ticks[2*count] */
 int srbm_debug_solve(int n, int count, const double* M_packed, const double* rhs, double* x, double* X_packed, int* ticks) {
@@ -491,17 +234,8 @@ int srbm_debug_solve(int n, int count, const double* M_packed, const double* rhs
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dX, bytes)); HIPCHK(tmp.alloc(&dr, vb)); HIPCHK(tmp.alloc(&dx, vb));
     HIPCHK(tmp.alloc(&dt, sizeof(int) * 2 * count));
-    HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dr, rhs, vb, hipMemcpyHostToDevice));
-    const size_t lds = DbgLds::XC * sizeof(double);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(srbm_k_debug_solve, dim3(count), dim3(DN_THREADS), lds, 0, n, dM, dr, dx, dX, dt);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(x, dx, vb, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(X_packed, dX, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ticks, dt, sizeof(int) * 2 * count, hipMemcpyDeviceToHost));
-    return 0;
+    return run_dense_hook(srbm_k_debug_solve, count, DbgLds::XC * sizeof(double), {{dM, M_packed, bytes}, {dr, rhs, vb}},
+                          {{x, dx, vb}, {X_packed, dX, bytes}, {ticks, dt, sizeof(int) * 2 * count}}, n, dM, dr, dx, dX, dt);
 }
 int srbm_debug_cholesky(int n, int count, const double* M_packed, double* L_packed, int* nreg) {
 #ifdef SRBM_LARGE
@@ -512,39 +246,24 @@ int srbm_debug_cholesky(int n, int count, const double* M_packed, double* L_pack
     double *dM = nullptr, *dL = nullptr; int* dr = nullptr;
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dL, bytes)); HIPCHK(tmp.alloc(&dr, sizeof(int) * count));
-    HIPCHK(hipMemcpy(dM, M_packed, bytes, hipMemcpyHostToDevice));
-    const size_t lds = DbgLds::X * sizeof(double);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(srbm_k_debug_cholesky), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(srbm_k_debug_cholesky, dim3(count), dim3(DN_THREADS), lds, 0, n, dM, dL, dr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(L_packed, dL, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(nreg, dr, sizeof(int) * count, hipMemcpyDeviceToHost));
-    return 0;
+    return run_dense_hook(srbm_k_debug_cholesky, count, DbgLds::X * sizeof(double), {{dM, M_packed, bytes}}, {{L_packed, dL, bytes}, {nreg, dr, sizeof(int) * count}},
+                          n, dM, dL, dr);
 }
-int srbm_debug_get_trace(srbm_batch* h, int inst, double* out256) {
+// dbg and dbg2 of one instance, adjacent in SrbmWork: 384 doubles
+int srbm_debug_get_trace(srbm_batch* h, int inst, double* out384) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out256, reinterpret_cast<const char*>(h->works + inst) + offsetof(SrbmWork, dbg), sizeof(double) * 384, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(h, {{out384, work_field(h, inst, offsetof(SrbmWork, dbg)), sizeof(double) * 384}});
 }
 
 // diagnostic: the spline variables of the linearisation point and of the QP minimiser of instance `inst`, with the column descriptors
 // (foot, type 0 force / 1 position, coordinate, local index) and the pin / substitution mask -- scripts/dev_attempts.py
 int srbm_debug_get_spline_step(srbm_batch* h, int inst, double* u_prev, double* u, int* cols4, int* fix) {
     if (!h || inst < 0 || inst >= h->batch || !u_prev || !u || !cols4 || !fix) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const char* W = reinterpret_cast<const char*>(h->works + inst);
-    HIPCHK(hipMemcpy(u_prev, W + offsetof(SrbmWork, u_prev), sizeof(double) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(u, W + offsetof(SrbmWork, u), sizeof(double) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cols4, W + offsetof(SrbmWork, col_ee), sizeof(int) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cols4 + SRBM_NUMAX, W + offsetof(SrbmWork, col_type), sizeof(int) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cols4 + 2 * SRBM_NUMAX, W + offsetof(SrbmWork, col_coord), sizeof(int) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cols4 + 3 * SRBM_NUMAX, W + offsetof(SrbmWork, col_local), sizeof(int) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(fix, W + offsetof(SrbmWork, fix_mask), sizeof(int) * SRBM_NUMAX, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t nd = sizeof(double) * SRBM_NUMAX, ni = sizeof(int) * SRBM_NUMAX;
+    auto W = [&](size_t offset) { return work_field(h, inst, offset); };
+    return fetch(h, {{u_prev, W(offsetof(SrbmWork, u_prev)), nd}, {u, W(offsetof(SrbmWork, u)), nd}, {cols4, W(offsetof(SrbmWork, col_ee)), ni},
+                     {cols4 + SRBM_NUMAX, W(offsetof(SrbmWork, col_type)), ni}, {cols4 + 2 * SRBM_NUMAX, W(offsetof(SrbmWork, col_coord)), ni},
+                     {cols4 + 3 * SRBM_NUMAX, W(offsetof(SrbmWork, col_local)), ni}, {fix, W(offsetof(SrbmWork, fix_mask)), ni}});
 }
 
 // device buffers + kernel attributes of a batch whose host parameters (h->hp, batch, device) are set; on failure everything
@@ -720,13 +439,11 @@ int srbm_get_solver_step_rule(const srbm_batch* h, double* tol_step, double* sta
 }
 int srbm_set_state_trajectory_warm_start(srbm_batch* h, const double* states) {
     if (!h || !states) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     HIPCHK(hipMemcpyAsync(h->d_state, states, sizeof(double) * 13 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(srbm_k_warm_start, dim3(h->batch), dim3(64), 0, h->stream, h->dp, h->insts, h->d_state);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 
 static int upload_inputs(srbm_batch* h, const double* state, const double* init_time, const double* ee) {
@@ -743,16 +460,14 @@ int srbm_create_initial_run(srbm_batch* h, const double* state, const double* ee
     HIPCHK(hipSetDevice(h->device));
     if (upload_inputs(h, state, nullptr, ee)) return -1;
     for (int it = 0; it < 10; it++) if (launch_step(h)) return -1;     // mpc.cpp:85-88: always 10 solves
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 int srbm_get_real_time_update(srbm_batch* h, const double* state, const double* init_time, const double* ee) {
     if (!h || !state || !init_time || !ee) return fail("bad arguments");
     HIPCHK(hipSetDevice(h->device));
     if (upload_inputs(h, state, init_time, ee)) return -1;
     if (launch_step(h)) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 int srbm_get_real_time_update_dev(srbm_batch* h, const double* state_dev, const double* time_dev, const double* ee_dev) {
     if (!h || !state_dev || !time_dev || !ee_dev) return fail("bad arguments");
@@ -767,8 +482,7 @@ static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs
     // (the lower-start attempt rests on the linearisation point being close to the new minimiser: true for the open-loop protocol, whose state IS
     //  node 1 of the plan; under a plant -- integration error every step, pushes -- it is repeated too often to pay: closed loop 62 k it/s with, 80 k without)
     pl.tol_step = h->hp.tol_step; pl.start_mu = pl.plant ? 0.0 : h->hp.start_mu;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     if (steps == 0) return 0;
     h->last_tol_step = pl.tol_step;
     // one launch for all steps (double time = i*info.integrator_dt, gait_opt_playground.cpp:84, is formed on the device)
@@ -776,23 +490,20 @@ static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs
     if (tm) HIPCHK(hipEventRecord(h->ev_start[h->ev_used], h->stream));
     // a batch larger than the chip, several steps: a resident grid takes (instance, step) items from the step queues (srbm_fused.hiph)
     const bool queued = h->queued_ok && h->batch > h->n_cu && steps > 1 && steps <= SRBM_QUEUE_MAX_STEPS && h->batch <= SRBM_QUEUE_MAX_BATCH;
-    h->last_launch_kernel = (queued ? 3 : 1) + (h->hp.N <= K3_SHORT_N ? 0 : 1);
+    const bool long_n = k3_long(h);
+    h->last_launch_kernel = (queued ? 3 : 1) + (long_n ? 1 : 0);          // the codes of srbm_debug_get_launch_info
     h->last_launch_steps = steps;
     if (queued) {
         if (!h->queues) HIPCHK(hipMalloc(&h->queues, sizeof(SrbmQueue) * SRBM_NQUEUES));
         hipLaunchKernelGGL(srbm_k_queue_init, dim3(SRBM_NQUEUES), dim3(256), 0, h->stream, h->queues, h->batch);
-        if (h->hp.N <= K3_SHORT_N)
-            hipLaunchKernelGGL(srbm_rti_queued, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
-        else
-            hipLaunchKernelGGL(srbm_rti_queued_long, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
-    } else if (h->hp.N <= K3_SHORT_N)
-        hipLaunchKernelGGL(srbm_rti_fused, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
+        const auto kernel = long_n ? srbm_rti_queued_long : srbm_rti_queued;
+        hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
+                           h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
+    } else {
+        const auto kernel = long_n ? srbm_rti_fused_long : srbm_rti_fused;
+        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                            h->d_state, h->d_time, h->d_ee, pl);
-    else
-        hipLaunchKernelGGL(srbm_rti_fused_long, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                           h->d_state, h->d_time, h->d_ee, pl);
+    }
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = steps; h->ev_used++; }
     HIPCHK(hipGetLastError());
     return 0;
@@ -816,16 +527,12 @@ int srbm_plant_set_state(srbm_batch* h, const double* state) {
     HIPCHK(hipSetDevice(h->device));
     if (plant_alloc(h)) return -1;
     HIPCHK(hipMemcpyAsync(h->d_plant, state, sizeof(double) * 13 * h->batch, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 int srbm_plant_get_state(srbm_batch* h, double* state) {
     if (!h || !state) return fail("bad arguments");
     if (!h->d_plant) return fail("the plant state has not been set (srbm_plant_set_state)");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(state, h->d_plant, sizeof(double) * 13 * h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(h, {{state, h->d_plant, sizeof(double) * 13 * h->batch}});
 }
 int srbm_plant_set_push(srbm_batch* h, const double* time, const double* impulse) {
     if (!h || (time == nullptr) != (impulse == nullptr)) return fail("bad arguments");
@@ -849,8 +556,7 @@ int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int subs
 // A/B measurements against the fused kernel
 int srbm_rti_advance_unfused(srbm_batch* h, int first_index, int steps) {
     if (!h || steps < 0) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     for (int i = 0; i < steps; i++) {
         const double time = (first_index + i) * h->hp.dt;
         hipLaunchKernelGGL(srbm_k_next_inputs, dim3(h->batch), dim3(64), 0, h->stream, h->dp, h->insts, time, h->d_state, h->d_time, h->d_ee);
@@ -868,21 +574,19 @@ void* srbm_stream(srbm_batch* h) { return h ? (void*)h->stream : nullptr; }
 
 int srbm_update_contact_times(srbm_batch* h, const double* times, int max_contacts) {
     if (!h || !times || max_contacts <= 0) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
     // the reference indexes the caller's vector with its own contact count (end_effector_splines.cpp:860-892): a vector that is
     // too short is an out-of-range read there, an error here
-    std::vector<SrbmInst> v;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    v.resize(h->batch);
-    HIPCHK(hipMemcpy(v.data(), h->insts, sizeof(SrbmInst) * (size_t)h->batch, hipMemcpyDeviceToHost));
-    for (int b = 0; b < h->batch; b++)
-        for (int ee = 0; ee < SRBM_NEE; ee++) {
-            int n = 0;
-            for (int i = 0; i < v[b].nk[ee]; i++) n += (v[b].kind[ee][i] <= SRBM_K_TD);
-            if (n > max_contacts)
-                return fail("srbm_update_contact_times: instance " + std::to_string(b) + " foot " + std::to_string(ee) + " has " + std::to_string(n) +
-                            " contact times, max_contacts is " + std::to_string(max_contacts));
-        }
+    std::string why;
+    if (each_inst(h, [&](int b, const SrbmInst& I) {
+            for (int ee = 0; ee < SRBM_NEE && why.empty(); ee++) {
+                int n = 0;
+                for (int i = 0; i < I.nk[ee]; i++) n += (I.kind[ee][i] <= SRBM_K_TD);
+                if (n > max_contacts)
+                    why = "srbm_update_contact_times: instance " + std::to_string(b) + " foot " + std::to_string(ee) + " has " + std::to_string(n) +
+                          " contact times, max_contacts is " + std::to_string(max_contacts);
+            }
+        })) return -1;
+    if (!why.empty()) return fail(why);
     void* d = nullptr;
     const size_t bytes = sizeof(double) * (size_t)h->batch * SRBM_NEE * max_contacts;
     if (batch_scratch(h, bytes, &d)) return -1;
@@ -891,8 +595,7 @@ int srbm_update_contact_times(srbm_batch* h, const double* times, int max_contac
     const int tot = h->batch * SRBM_NEE;
     hipLaunchKernelGGL(srbm_k_set_contact_times, dim3((tot + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, static_cast<const double*>(d), max_contacts);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 
 // ---------------- bilevel (gait) step: mpc::GaitOptimizer for the batch ----------------
@@ -952,8 +655,7 @@ static int alloc_gait(srbm_gait* g) {
     HIPCHK(hipMemsetAsync(g->xk, 0, sizeof(double) * SRBM_GAIT_NV * B, h->stream));
     HIPCHK(hipMemsetAsync(g->step, 0, sizeof(double) * SRBM_GAIT_NV * B, h->stream));
     HIPCHK(hipMemsetAsync(g->dHdth, 0, sizeof(double) * SRBM_GAIT_NV * B, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 
 int srbm_gait_create(srbm_batch* h, srbm_gait** out) {
@@ -974,33 +676,25 @@ int srbm_gait_destroy(srbm_gait* g) {
 int srbm_gait_set_contact_times_from_trajectory(srbm_gait* g) {
     if (!g) return fail("bad arguments");
     srbm_batch* h = g->h;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_gait_read_contact_times, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, g->xk, g->counts);
     HIPCHK(hipGetLastError());
     return 0;
 }
 int srbm_gait_get_contact_times(srbm_gait* g, double* xk, int* counts) {
     if (!g || !xk || !counts) return fail("bad arguments");
-    HIPCHK(hipSetDevice(g->h->device));
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    HIPCHK(hipMemcpy(xk, g->xk, sizeof(double) * SRBM_GAIT_NV * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(counts, g->counts, sizeof(int) * SRBM_NEE * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t B = g->h->batch;
+    return fetch(g->h, {{xk, g->xk, sizeof(double) * SRBM_GAIT_NV * B}, {counts, g->counts, sizeof(int) * SRBM_NEE * B}});
 }
 int srbm_gait_set_step(srbm_gait* g, const double* step) {
     if (!g || !step) return fail("bad arguments");
     HIPCHK(hipSetDevice(g->h->device));
     HIPCHK(hipMemcpyAsync(g->step, step, sizeof(double) * SRBM_GAIT_NV * (size_t)g->h->batch, hipMemcpyHostToDevice, g->h->stream));
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    return 0;
+    return srbm_synchronize(g->h);
 }
 int srbm_gait_get_step(srbm_gait* g, double* step) {
     if (!g || !step) return fail("bad arguments");
-    HIPCHK(hipSetDevice(g->h->device));
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    HIPCHK(hipMemcpy(step, g->step, sizeof(double) * SRBM_GAIT_NV * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(g->h, {{step, g->step, sizeof(double) * SRBM_GAIT_NV * (size_t)g->h->batch}});
 }
 // MPC::ComputeDerivativeTerms (mpc.cpp:1047-1069): KKT sensitivity d = [dz; dlam; dnu] of the last QP solution
 int srbm_gait_compute_sensitivity(srbm_gait* g) {
@@ -1010,8 +704,7 @@ int srbm_gait_compute_sensitivity(srbm_gait* g) {
         return fail("srbm_gait_compute_sensitivity: the last solve of this batch ran with the step rule (tol_step > 0): its multipliers are not at the "
                     "gap tolerance the KKT sensitivity needs -- call srbm_set_solver_step_rule(h, 0, start_mu) before the solve that is differentiated "
                     "(srbm_gait_rti_advance does so by itself)");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k3_normal_matrix, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works);
     hipLaunchKernelGGL(srbm_k_gait_sensitivity, dim3(h->batch), dim3(KG_THREADS), KG_DYN_LDS_BYTES, h->stream, h->dp, h->insts, h->works, g->gw);
     HIPCHK(hipGetLastError());
@@ -1034,11 +727,9 @@ int srbm_gait_compute_gradient(srbm_gait* g) {
 // srbm_export_qp: it runs the SAME per-item code the gradient kernel contracts (gait_param_partial_item), with a dense emitter.
 int srbm_gait_get_param_partials(srbm_batch* h, int inst, int ee, int idx, double* dA, double* dG, double* db, double* dh) {
     if (!h || inst < 0 || inst >= h->batch || ee < 0 || ee >= SRBM_NEE || idx < 0 || !dA || !dG || !db || !dh) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (use_batch(h)) return -1;
     SrbmInst I;
-    HIPCHK(hipMemcpy(&I, h->insts + inst, sizeof(SrbmInst), hipMemcpyDeviceToHost));
+    if (fetch(h, {{&I, h->insts + inst, sizeof(SrbmInst)}})) return -1;
     const size_t n = I.n, me = I.n_eq, mi = I.n_ineq;
     if (n == 0 || me == 0) return fail("srbm_gait_get_param_partials: no QP has been solved yet");
     double* d = nullptr;
@@ -1050,12 +741,9 @@ int srbm_gait_get_param_partials(srbm_batch* h, int inst, int ee, int idx, doubl
     hipLaunchKernelGGL(srbm_k_gait_param_partials, dim3(1), dim3(KH_THREADS), 0, h->stream, h->dp, h->insts + inst, h->works + inst, ee, idx,
                        d, d + me * n, d + me * n + mi * n, derr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
     int err = 0;
-    HIPCHK(hipMemcpy(dA, d, sizeof(double) * me * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(dG, d + me * n, sizeof(double) * mi * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(db, d + me * n + mi * n, sizeof(double) * me, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&err, derr, sizeof(int), hipMemcpyDeviceToHost));
+    if (fetch(h, {{dA, d, sizeof(double) * me * n}, {dG, d + me * n, sizeof(double) * mi * n}, {db, d + me * n + mi * n, sizeof(double) * me},
+                  {&err, derr, sizeof(int)}})) return -1;
     std::memset(dh, 0, sizeof(double) * mi);
     if (err & SRBM_ERR_CAPACITY) return fail("srbm_gait_get_param_partials: contact index out of range");
     if (err) return fail("srbm_gait_get_param_partials: spline lookup failed (error bits " + std::to_string(err) + ")");
@@ -1063,11 +751,8 @@ int srbm_gait_get_param_partials(srbm_batch* h, int inst, int ee, int idx, doubl
 }
 int srbm_gait_get_gradient(srbm_gait* g, double* dHdth, int* valid) {
     if (!g || !dHdth) return fail("bad arguments");
-    HIPCHK(hipSetDevice(g->h->device));
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    HIPCHK(hipMemcpy(dHdth, g->dHdth, sizeof(double) * SRBM_GAIT_NV * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    if (valid) HIPCHK(hipMemcpy(valid, g->valid, sizeof(int) * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t B = g->h->batch;
+    return fetch(g->h, {{dHdth, g->dHdth, sizeof(double) * SRBM_GAIT_NV * B}, {valid, g->valid, sizeof(int) * B}});
 }
 int srbm_gait_get_sensitivity(srbm_gait* g, double* d, int ld) {
     if (!g || !d || ld <= 0) return fail("bad arguments");
@@ -1080,30 +765,33 @@ int srbm_gait_get_sensitivity(srbm_gait* g, double* d, int ld) {
     HIPCHK(hipMemsetAsync(dev, 0, bytes, h->stream));
     hipLaunchKernelGGL(srbm_k_gait_pack_d, dim3(h->batch), dim3(128), 0, h->stream, h->dp, h->insts, h->works, g->gw, dev, ld);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(d, dev, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(h, {{d, dev, bytes}});
+}
+// the LP of the gait step on the gradient dHdth and the time in h->d_time (srbm_gait.hiph)
+static void launch_gait_lp(srbm_gait* g) {
+    srbm_batch* h = g->h;
+    hipLaunchKernelGGL(srbm_k_gait_lp, dim3(h->batch), dim3(LP_THREADS), 0, h->stream, h->dp, h->insts, g->xk, g->counts, g->dHdth, h->d_time,
+                       g->step, g->pred_red, g->lp_status);
+}
+// deriv_ready of every instance: `force` (0 / 1), or -1 for "a gradient exists and its LP was solved"
+static void launch_gait_ready(srbm_gait* g, int force) {
+    srbm_batch* h = g->h;
+    hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, g->valid, g->lp_status, g->ready, force);
 }
 // GaitOptimizer::OptimizeContactTimes (gait_optimizer.cpp:185-364): the LP over the contact-time step; time[batch]
 int srbm_gait_optimize_contact_times(srbm_gait* g, const double* time) {
     if (!g || !time) return fail("bad arguments");
     srbm_batch* h = g->h;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     HIPCHK(hipMemcpyAsync(h->d_time, time, sizeof(double) * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
-    const int threads = h->batch * SRBM_NEE;
-    hipLaunchKernelGGL(srbm_k_gait_lp, dim3(h->batch), dim3(LP_THREADS), 0, h->stream, h->dp, h->insts, g->xk, g->counts, g->dHdth, h->d_time,
-                       g->step, g->pred_red, g->lp_status);
+    launch_gait_lp(g);
     HIPCHK(hipGetLastError());
     return 0;
 }
 int srbm_gait_get_lp_result(srbm_gait* g, int* lp_status, double* pred_red) {
     if (!g) return fail("bad arguments");
-    HIPCHK(hipSetDevice(g->h->device));
-    HIPCHK(hipStreamSynchronize(g->h->stream));
-    if (lp_status) HIPCHK(hipMemcpy(lp_status, g->lp_status, sizeof(int) * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    if (pred_red) HIPCHK(hipMemcpy(pred_red, g->pred_red, sizeof(double) * (size_t)g->h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t B = g->h->batch;
+    return fetch(g->h, {{lp_status, g->lp_status, sizeof(int) * B}, {pred_red, g->pred_red, sizeof(double) * B}});
 }
 // candidates -> 10*B solves -> argmin + install; inputs already in h->d_state / d_time / d_ee
 static int line_search_core(srbm_gait* g, bool use_ready_mask) {
@@ -1128,20 +816,14 @@ int srbm_gait_line_search(srbm_gait* g, const double* state, const double* time,
     HIPCHK(hipSetDevice(h->device));
     if (upload_inputs(h, state, time, ee)) return -1;
     if (line_search_core(g, false)) return -1;
-    const int B = h->batch;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (imin) HIPCHK(hipMemcpy(imin, g->imin, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
-    if (costs) HIPCHK(hipMemcpy(costs, g->costs, sizeof(double) * SRBM_LS_SIZE * (size_t)B, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t B = h->batch;
+    return fetch(h, {{imin, g->imin, sizeof(int) * B}, {costs, g->costs, sizeof(double) * SRBM_LS_SIZE * B}});
 }
 // MPCController::GaitOpt (mpc_controller.cpp:518-566): gradient + LP at `time`; sets deriv_ready per instance
 static int gait_opt_core(srbm_gait* g) {        // time already in h->d_time
-    srbm_batch* h = g->h;
     if (srbm_gait_compute_gradient(g)) return -1;
-    const int threads = h->batch * SRBM_NEE;
-    hipLaunchKernelGGL(srbm_k_gait_lp, dim3(h->batch), dim3(LP_THREADS), 0, h->stream, h->dp, h->insts, g->xk, g->counts, g->dHdth, h->d_time,
-                       g->step, g->pred_red, g->lp_status);
-    hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, g->valid, g->lp_status, g->ready, -1);
+    launch_gait_lp(g);
+    launch_gait_ready(g, -1);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1153,8 +835,7 @@ static int gait_opt_core(srbm_gait* g) {        // time already in h->d_time
 int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq) {
     if (!g || steps < 0 || gait_opt_freq <= 0) return fail("bad arguments");
     srbm_batch* h = g->h;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     for (int i = 0; i < steps; i++) {
         const int run_num = first_run_num + i;
         const double time = run_num * h->hp.dt;
@@ -1162,7 +843,7 @@ int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_o
         if (run_num % gait_opt_freq == 0 && run_num > 0) {
             // instances without a ready gradient get the plain update through the same 10-candidate batch (zero step)
             if (line_search_core(g, true)) return -1;
-            hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, g->valid, g->lp_status, g->ready, 0);
+            launch_gait_ready(g, 0);
         } else if ((run_num + 1) % gait_opt_freq == 0 && run_num > 0) {
             // the solve the gradient differentiates: to the reference's gap criterion (the as-coded KKT sensitivity divides by the slacks, so it
             // needs the duals Clarabel's tolerance gives); every other solve of the protocol -- plain steps, the 10 candidates of a line
@@ -1171,29 +852,25 @@ int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_o
             if (gait_opt_core(g)) return -1;
         } else {
             if (launch_step(h)) return -1;
-            hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, g->valid, g->lp_status, g->ready, 0);
+            launch_gait_ready(g, 0);
         }
         HIPCHK(hipGetLastError());
     }
     return 0;
 }
-/* status / stats of the candidates of the last line search: status[batch][10], iters[batch][10] (diagnostic) */
 // diagnostic / test hook: the batch of line-search candidates (LS_SIZE per instance, candidate c of instance b at index b * LS_SIZE + c), owned by
 // the gait handle -- for the read-back entries (status, sizes, srbm_export_qp) only
 srbm_batch* srbm_gait_debug_candidates(srbm_gait* g) { return g ? g->ls : nullptr; }
+// status and error bits of the candidates of the last line search: status[batch * LS_SIZE], err[batch * LS_SIZE] (diagnostic)
 int srbm_gait_get_candidate_status(srbm_gait* g, int* status, int* err) {
     if (!g || !status || !err) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(g->ls, v)) return -1;
-    for (int b = 0; b < g->ls->batch; b++) { status[b] = v[b].status; err[b] = v[b].err | v[b].err_acc; }
-    return 0;
+    return each_inst(g->ls, [&](int b, const SrbmInst& I) { status[b] = I.status; err[b] = I.err | I.err_acc; });
 }
 
 // MPC::AdjustForCurrentContacts (mpc.cpp:1195-1203): time[batch], in_contact[batch][4]
 int srbm_adjust_for_current_contacts(srbm_batch* h, const double* time, const int* in_contact) {
     if (!h || !time || !in_contact) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     void* dcv = nullptr;
     const size_t B = h->batch;
     if (batch_scratch(h, sizeof(int) * 4 * B, &dcv)) return -1;
@@ -1203,8 +880,7 @@ int srbm_adjust_for_current_contacts(srbm_batch* h, const double* time, const in
     const int tot = h->batch * SRBM_NEE;
     hipLaunchKernelGGL(srbm_k_adjust_for_current_contacts, dim3((tot + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, h->d_time, dc);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return srbm_synchronize(h);
 }
 
 int srbm_enable_kernel_timing(srbm_batch* h, int max_launches) {
@@ -1220,8 +896,7 @@ int srbm_enable_kernel_timing(srbm_batch* h, int max_launches) {
 }
 int srbm_get_kernel_timing(srbm_batch* h, double* total_ms, int* launches) {
     if (!h || !total_ms || !launches) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (srbm_synchronize(h)) return -1;
     double tot = 0;
     for (size_t i = 0; i < h->ev_used; i++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_start[i], h->ev_stop[i])); tot += ms; }
     *total_ms = tot; *launches = (int)h->ev_used;
@@ -1229,8 +904,7 @@ int srbm_get_kernel_timing(srbm_batch* h, double* total_ms, int* launches) {
 }
 int srbm_get_kernel_timings(srbm_batch* h, double* ms_each, int max_launches, int* launches) {
     if (!h || !ms_each || !launches || max_launches < 0) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (srbm_synchronize(h)) return -1;
     *launches = (int)h->ev_used;
     for (size_t i = 0; i < h->ev_used && (int)i < max_launches; i++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_start[i], h->ev_stop[i])); ms_each[i] = ms; }
     return 0;
@@ -1238,10 +912,7 @@ int srbm_get_kernel_timings(srbm_batch* h, double* ms_each, int max_launches, in
 // per instance: the running total of factorisations (diagnostic: scripts/dev_dispatch_order.py)
 int srbm_debug_get_instance_iters(srbm_batch* h, double* iters /* [batch] */) {
     if (!h || !iters) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) iters[b] = v[b].acc_iters;
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { iters[b] = I.acc_iters; });
 }
 // which kernel the last srbm_rti_advance / srbm_closed_loop_advance with steps > 0 took (tests/test_gpu_launch_equivalence.py):
 // out4 = {CUs of the device, kernel (0 none yet, 1 srbm_rti_fused, 2 srbm_rti_fused_long, 3 srbm_rti_queued, 4 srbm_rti_queued_long), its steps,
@@ -1253,20 +924,15 @@ int srbm_debug_get_launch_info(const srbm_batch* h, int* out4) {
 }
 int srbm_get_work_counters(srbm_batch* h, double* total_ipm_iterations, double* total_algorithmic_flops) {
     if (!h) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<SrbmInst> v(h->batch);
-    HIPCHK(hipMemcpy(v.data(), h->insts, sizeof(SrbmInst) * (size_t)h->batch, hipMemcpyDeviceToHost));
     double it = 0, fl = 0;
-    for (auto& I : v) { it += I.acc_iters; fl += I.acc_flops; }
+    if (each_inst(h, [&](int, const SrbmInst& I) { it += I.acc_iters; fl += I.acc_flops; })) return -1;
     if (total_ipm_iterations) *total_ipm_iterations = it;
     if (total_algorithmic_flops) *total_algorithmic_flops = fl;
     return 0;
 }
 int srbm_pack_results_dev(srbm_batch* h, double* out_dev, int ld) {
     if (!h || !out_dev || ld < 8) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_pack_results, dim3(h->batch), dim3(64), 0, h->stream, h->dp, h->insts, h->works, out_dev, ld);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1279,9 +945,7 @@ int srbm_pack_results(srbm_batch* h, double* out, int ld) {
     const size_t bytes = sizeof(double) * (size_t)h->batch * ld;
     if (batch_scratch(h, bytes, &d)) return -1;
     if (srbm_pack_results_dev(h, static_cast<double*>(d), ld)) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return fetch(h, {{out, d, bytes}});
 }
 
 // ---------------- multi-GPU: RCCL all-gather of the result records (include/srbm_rti.h) ----------------
@@ -1376,64 +1040,33 @@ int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev) {
 }
 
 // ---------------- getters ----------------
-static int fetch_insts(srbm_batch* h, std::vector<SrbmInst>& v) {
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    v.resize(h->batch);
-    HIPCHK(hipMemcpy(v.data(), h->insts, sizeof(SrbmInst) * (size_t)h->batch, hipMemcpyDeviceToHost));
-    return 0;
-}
 int srbm_get_sizes(srbm_batch* h, int* sizes) {
     if (!h || !sizes) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) {
+    return each_inst(h, [&](int b, const SrbmInst& I) {
         int* s = sizes + 8 * b;
-        s[0] = v[b].n; s[1] = v[b].m; s[2] = v[b].n_eq; s[3] = v[b].n_ineq; s[4] = v[b].nfv; s[5] = v[b].npv; s[6] = v[b].n_td; s[7] = v[b].n_samples;
-    }
-    return 0;
+        s[0] = I.n; s[1] = I.m; s[2] = I.n_eq; s[3] = I.n_ineq; s[4] = I.nfv; s[5] = I.npv; s[6] = I.n_td; s[7] = I.n_samples;
+    });
 }
 int srbm_get_status(srbm_batch* h, int* status, int* err) {
     if (!h || !status) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) { status[b] = v[b].status; if (err) err[b] = v[b].err; }
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { status[b] = I.status; if (err) err[b] = I.err; });
 }
 // QP objective at the raw QP minimiser (the "QP Cost" column of MPC::PrintStatLineToFile, mpc.cpp:989): cost[batch]
 int srbm_get_qp_cost(srbm_batch* h, double* cost) {
     if (!h || !cost) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) cost[b] = v[b].qp_cost;
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { cost[b] = I.qp_cost; });
 }
 int srbm_get_stats(srbm_batch* h, double* stats) {
     if (!h || !stats) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) {
+    return each_inst(h, [&](int b, const SrbmInst& I) {
         double* s = stats + 8 * b;
-        s[0] = v[b].alpha; s[1] = v[b].cost; s[2] = v[b].eq_violation; s[3] = v[b].step_norm; s[4] = v[b].qp_iters;
-        s[5] = v[b].res_primal; s[6] = v[b].res_dual; s[7] = v[b].gap;
-    }
-    return 0;
+        s[0] = I.alpha; s[1] = I.cost; s[2] = I.eq_violation; s[3] = I.step_norm; s[4] = I.qp_iters; s[5] = I.res_primal; s[6] = I.res_dual; s[7] = I.gap;
+    });
 }
 int srbm_get_trajectory_states(srbm_batch* h, double* states) {
     if (!h || !states) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
     const int len = (h->hp.N + 1) * 13;
-    for (int b = 0; b < h->batch; b++) std::memcpy(states + (size_t)b * len, v[b].states, sizeof(double) * len);
-    return 0;
-}
-static int fetch_work_field(srbm_batch* h, size_t offset, size_t count, double* out, int ld) {
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if ((size_t)ld < count) return fail("leading dimension too small");
-    HIPCHK(hipMemcpy2D(out, sizeof(double) * ld, reinterpret_cast<const char*>(h->works) + offset, sizeof(SrbmWork), sizeof(double) * count,
-                       h->batch, hipMemcpyDeviceToHost));
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { std::memcpy(states + (size_t)b * len, I.states, sizeof(double) * len); });
 }
 int srbm_get_qp_solution(srbm_batch* h, double* x, int ld) {
     if (!h || !x) return fail("bad arguments");
@@ -1451,10 +1084,8 @@ int srbm_get_dual_solution(srbm_batch* h, double* z, double* s, int ld) {
 }
 int srbm_get_knots(srbm_batch* h, int inst, double* times, int* kinds, int* nk, double* fvals, double* pvals, double* box) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<SrbmInst> v(1);
-    HIPCHK(hipMemcpy(v.data(), h->insts + inst, sizeof(SrbmInst), hipMemcpyDeviceToHost));
+    if (fetch(h, {{v.data(), h->insts + inst, sizeof(SrbmInst)}})) return -1;
     const SrbmInst& I = v[0];
     for (int ee = 0; ee < SRBM_NEE; ee++) {
         if (nk) nk[ee] = I.nk[ee];
@@ -1472,12 +1103,9 @@ int srbm_get_knots(srbm_batch* h, int inst, double* times, int* kinds, int* nk, 
 // Dense expansion of the structured QP into the reference's row/column layout.
 int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* Pm, double* q) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<SrbmInst> vi(1);
     std::vector<SrbmWork> vw(1);
-    HIPCHK(hipMemcpy(vi.data(), h->insts + inst, sizeof(SrbmInst), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(vw.data(), h->works + inst, sizeof(SrbmWork), hipMemcpyDeviceToHost));
+    if (fetch(h, {{vi.data(), h->insts + inst, sizeof(SrbmInst)}, {vw.data(), h->works + inst, sizeof(SrbmWork)}})) return -1;
     const SrbmInst& I = vi[0];
     const SrbmWork& W = vw[0];
     const SrbmParams& P = h->hp;
@@ -1610,10 +1238,8 @@ static const char* check_record(const SrbmParams& P, const srbm_trajectory& t) {
 int srbm_sizeof_trajectory(void) { return (int)sizeof(srbm_trajectory); }
 int srbm_get_trajectory(srbm_batch* h, int first, int count, srbm_trajectory* out) {
     if (!h || !out || first < 0 || count < 0 || first + count > h->batch) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<SrbmInst> v(count);
-    HIPCHK(hipMemcpy(v.data(), h->insts + first, sizeof(SrbmInst) * (size_t)count, hipMemcpyDeviceToHost));
+    if (fetch(h, {{v.data(), h->insts + first, sizeof(SrbmInst) * (size_t)count}})) return -1;
     for (int i = 0; i < count; i++) inst_to_record(h->hp, v[i], out + i);
     return 0;
 }
@@ -1622,10 +1248,8 @@ int srbm_set_warm_start_trajectory(srbm_batch* h, int first, int count, const sr
     if (!h || !trajs || first < 0 || count < 0 || first + count > h->batch) return fail("bad arguments");
     for (int i = 0; i < count; i++)
         if (const char* why = check_record(h->hp, trajs[i])) return fail("srbm_set_warm_start_trajectory: record " + std::to_string(i) + ": " + why);
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<SrbmInst> v(count);
-    HIPCHK(hipMemcpy(v.data(), h->insts + first, sizeof(SrbmInst) * (size_t)count, hipMemcpyDeviceToHost));
+    if (fetch(h, {{v.data(), h->insts + first, sizeof(SrbmInst) * (size_t)count}})) return -1;
     for (int i = 0; i < count; i++) {
         SrbmInst& I = v[i];
         const srbm_trajectory& t = trajs[i];
@@ -1708,33 +1332,25 @@ int srbm_convert_tangent_to_manifold(const double* tangent12, double* state13) {
 }
 int srbm_eval_trajectory(srbm_batch* h, const double* time, double* force, double* pos, int* in_contact) {
     if (!h || !time) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
-    const size_t B = h->batch, nf = sizeof(double) * 12 * B, total = sizeof(double) * B + 2 * nf + sizeof(int) * 4 * B;
-    void *dv = nullptr, *hv = nullptr;
-    if (batch_stage(h, total, &dv, &hv)) return -1;
-    double* d_t = static_cast<double*>(dv);
-    double* d_f = d_t + B;
-    double* d_p = d_f + 12 * B;
-    int* d_c = reinterpret_cast<int*>(d_p + 12 * B);
-    char* hb = static_cast<char*>(hv);
-    memcpy(hb, time, sizeof(double) * B);
-    HIPCHK(hipMemcpyAsync(d_t, hb, sizeof(double) * B, hipMemcpyHostToDevice, h->stream));
-    const int tot = h->batch * SRBM_NEE;
-    hipLaunchKernelGGL(srbm_k_eval_trajectory, dim3((tot + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, d_t, d_f, d_p, d_c);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hb + sizeof(double) * B, d_f, total - sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+    if (use_batch(h)) return -1;
+    const size_t B = h->batch;
+    Carve c;                                          // in: time; out: force, pos, in_contact
+    const auto t = c.add<double>(B), f = c.add<double>(12 * B), ps = c.add<double>(12 * B);
+    const auto ic = c.add<int>(4 * B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(t), time, t.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(t), c.host(t), t.bytes(), hipMemcpyHostToDevice, h->stream));
+    if (srbm_eval_trajectory_dev(h, c.dev(t), c.dev(f), c.dev(ps), c.dev(ic))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(f), c.dev(f), Carve::span(f, ic), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const char* o = hb + sizeof(double) * B;
-    if (force) memcpy(force, o, nf);
-    if (pos) memcpy(pos, o + nf, nf);
-    if (in_contact) memcpy(in_contact, o + 2 * nf, sizeof(int) * 4 * B);
+    if (force) memcpy(force, c.host(f), f.bytes());
+    if (pos) memcpy(pos, c.host(ps), ps.bytes());
+    if (in_contact) memcpy(in_contact, c.host(ic), ic.bytes());
     return 0;
 }
 int srbm_eval_trajectory_dev(srbm_batch* h, const double* time_dev, double* force_dev, double* pos_dev, int* in_contact_dev) {
     if (!h || !time_dev || !force_dev || !pos_dev || !in_contact_dev) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     const int tot = h->batch * SRBM_NEE;
     hipLaunchKernelGGL(srbm_k_eval_trajectory, dim3((tot + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, time_dev, force_dev, pos_dev, in_contact_dev);
     HIPCHK(hipGetLastError());
@@ -1747,70 +1363,47 @@ int srbm_get_ee_box_center(const srbm_batch* h, double* centers) {
 }
 int srbm_get_cost(srbm_batch* h, double* cost) {
     if (!h || !cost) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) cost[b] = v[b].cost;
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { cost[b] = I.cost; });
 }
 // merit[b] = cost + mu |dynamics defect|_1 of the trajectory after the last solve (MPC::GetMeritValue, mpc.cpp:749-753, mu = 5000) and
 // the directional derivative of the merit along the last step (GetMeritGradient, :783-788): the 'Merit' / 'Merit dd' columns
 int srbm_get_merit(srbm_batch* h, double* merit, double* merit_dd) {
     if (!h || !merit) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) { merit[b] = v[b].cost + h->hp.merit_mu * v[b].eq_violation; if (merit_dd) merit_dd[b] = v[b].merit_dd; }
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { merit[b] = I.cost + h->hp.merit_mu * I.eq_violation; if (merit_dd) merit_dd[b] = I.merit_dd; });
 }
 int srbm_get_avg_cost(srbm_batch* h, double* avg) {
     if (!h || !avg) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) avg[b] = v[b].cost_sum / v[b].run_num;      // (0/0 = NaN before the first solve, as the reference's)
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { avg[b] = I.cost_sum / I.run_num; });      // (0/0 = NaN before the first solve, as the reference's)
 }
 int srbm_get_status_accumulated(srbm_batch* h, int* acc) {
     if (!h || !acc) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) { acc[4 * b] = v[b].err_acc | v[b].err; acc[4 * b + 1] = v[b].n_solves; acc[4 * b + 2] = v[b].n_not_solved; acc[4 * b + 3] = v[b].n_maxiter; }
-    return 0;
-}
-__global__ void srbm_k_clear_acc(const SrbmParams* __restrict__ Pp, SrbmInst* __restrict__ insts) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= Pp->batch) return;
-    insts[b].err_acc = 0; insts[b].n_solves = 0; insts[b].n_not_solved = 0; insts[b].n_maxiter = 0;
-    insts[b].n_low_tried = 0; insts[b].n_low_failed = 0; insts[b].n_step_rule = 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) {
+        acc[4 * b] = I.err_acc | I.err; acc[4 * b + 1] = I.n_solves; acc[4 * b + 2] = I.n_not_solved; acc[4 * b + 3] = I.n_maxiter;
+    });
 }
 int srbm_clear_status_accumulators(srbm_batch* h) {
     if (!h) return fail("bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_clear_acc, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts);
     HIPCHK(hipGetLastError());
     return 0;
 }
 int srbm_get_solver_counters(srbm_batch* h, long long* c4) {
     if (!h || !c4) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    c4[0] = c4[1] = c4[2] = c4[3] = 0;
-    for (auto& I : v) { c4[0] += I.n_solves; c4[1] += I.n_step_rule; c4[2] += I.n_low_tried; c4[3] += I.n_low_failed; }
+    long long c[4] = {0, 0, 0, 0};
+    if (each_inst(h, [&](int, const SrbmInst& I) { c[0] += I.n_solves; c[1] += I.n_step_rule; c[2] += I.n_low_tried; c[3] += I.n_low_failed; })) return -1;
+    std::memcpy(c4, c, sizeof(c));
     return 0;
 }
 int srbm_get_solve_flags(srbm_batch* h, int* flags) {
     if (!h || !flags) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
-    for (int b = 0; b < h->batch; b++) flags[b] = (v[b].last_rule ? 1 : 0) | ((v[b].last_low & 1) ? 2 : 0) | ((v[b].last_low & 2) ? 4 : 0);
-    return 0;
+    return each_inst(h, [&](int b, const SrbmInst& I) { flags[b] = (I.last_rule ? 1 : 0) | ((I.last_low & 1) ? 2 : 0) | ((I.last_low & 2) ? 4 : 0); });
 }
 int srbm_result_record_doubles(int N) { return 8 + 12 * (N + 1) + SRBM_NUMAX + 12 * (N + 1) + 6 * SRBM_NSMAX + 16 * (N - 3) + 16 + 36; }
 int srbm_get_executed_mfma(srbm_batch* h, double* total) {
     if (!h || !total) return fail("bad arguments");
-    std::vector<SrbmInst> v;
-    if (fetch_insts(h, v)) return -1;
     double t = 0;
-    for (auto& I : v) t += I.acc_mfma;
+    if (each_inst(h, [&](int, const SrbmInst& I) { t += I.acc_mfma; })) return -1;
     *total = t;
     return 0;
 }
@@ -1826,81 +1419,60 @@ int srbm_set_leg_kinematics(srbm_batch* h, const srbm_leg_kinematics* legs) {
 static int need_legs(srbm_batch* h) { return h->hp.has_legs ? 0 : fail("the leg geometry has not been set (srbm_set_leg_kinematics)"); }
 int srbm_forward_kinematics(srbm_batch* h, const double* q, double* ee) {
     if (!h || !q || !ee) return fail("bad arguments");
-    if (need_legs(h)) return -1;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (need_legs(h) || use_batch(h)) return -1;
     const size_t B = h->batch;
-    void* dv = nullptr;
-    if (batch_scratch(h, sizeof(double) * (19 + 12) * B, &dv)) return -1;
-    double* dq = static_cast<double*>(dv);
-    double* de = dq + 19 * B;
-    HIPCHK(hipMemcpyAsync(dq, q, sizeof(double) * 19 * B, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(srbm_k_forward_kinematics, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, dq, de);
+    Carve c;
+    const auto dq = c.add<double>(19 * B), de = c.add<double>(12 * B);
+    if (c.scratch(h)) return -1;
+    HIPCHK(hipMemcpyAsync(c.dev(dq), q, dq.bytes(), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(srbm_k_forward_kinematics, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, c.dev(dq), c.dev(de));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(ee, de, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ee, c.dev(de), de.bytes(), hipMemcpyDeviceToHost));
     return 0;
 }
 int srbm_inverse_kinematics(srbm_batch* h, const double* state, const double* ee, const double* q_guess, double* q_out, int* iters, int* status) {
     if (!h || !state || !ee || !q_guess || !q_out) return fail("bad arguments");
-    if (need_legs(h)) return -1;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (need_legs(h) || use_batch(h)) return -1;
     const size_t B = h->batch;
-    void* dv = nullptr;
-    if (batch_scratch(h, sizeof(double) * (13 + 12 + 19 + 19) * B + sizeof(int) * 5 * B, &dv)) return -1;
-    double* ds = static_cast<double*>(dv);
-    double* de = ds + 13 * B;
-    double* dg = de + 12 * B;
-    double* dq = dg + 19 * B;
-    int* di = reinterpret_cast<int*>(dq + 19 * B);
-    int* dst = di + 4 * B;
-    HIPCHK(hipMemcpyAsync(ds, state, sizeof(double) * 13 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(de, ee, sizeof(double) * 12 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dg, q_guess, sizeof(double) * 19 * B, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(srbm_k_inverse_kinematics, dim3(h->batch), dim3(SRBM_IK_THREADS), 0, h->stream, h->dp, ds, de, dg, dq, di, dst);
+    Carve c;
+    const auto ds = c.add<double>(13 * B), de = c.add<double>(12 * B), dg = c.add<double>(19 * B), dq = c.add<double>(19 * B);
+    const auto di = c.add<int>(4 * B), dst = c.add<int>(B);
+    if (c.scratch(h)) return -1;
+    HIPCHK(hipMemcpyAsync(c.dev(ds), state, ds.bytes(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(c.dev(de), ee, de.bytes(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(c.dev(dg), q_guess, dg.bytes(), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(srbm_k_inverse_kinematics, dim3(h->batch), dim3(SRBM_IK_THREADS), 0, h->stream, h->dp, c.dev(ds), c.dev(de), c.dev(dg), c.dev(dq),
+                       c.dev(di), c.dev(dst));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(q_out, dq, sizeof(double) * 19 * B, hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, di, sizeof(int) * 4 * B, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dst, sizeof(int) * B, hipMemcpyDeviceToHost));
-    return 0;
+    return copy_each({{q_out, c.dev(dq), dq.bytes()}, {iters, c.dev(di), di.bytes()}, {status, c.dev(dst), dst.bytes()}}, hipMemcpyDeviceToHost);
 }
 int srbm_get_targets_from_traj(srbm_batch* h, const double* time, double* q_des, double* v_des, double* force_des, int* status) {
     if (!h || !time || !q_des || !v_des || !force_des) return fail("bad arguments");
-    if (need_legs(h)) return -1;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
-    const size_t B = h->batch, nin = sizeof(double) * (1 + 19) * B, total = sizeof(double) * (1 + 19 + 18 + 12) * B + sizeof(int) * B;
-    void *dv = nullptr, *hv = nullptr;
-    if (batch_stage(h, total, &dv, &hv)) return -1;
-    double* dt_ = static_cast<double*>(dv);
-    double* dq = dt_ + B;
-    double* dvv = dq + 19 * B;
-    double* df = dvv + 18 * B;
-    int* dst = reinterpret_cast<int*>(df + 12 * B);
-    char* hb = static_cast<char*>(hv);
-    memcpy(hb, time, sizeof(double) * B);
-    memcpy(hb + sizeof(double) * B, q_des, sizeof(double) * 19 * B);
-    HIPCHK(hipMemcpyAsync(dv, hb, nin, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(srbm_k_targets_from_traj, dim3(h->batch), dim3(SRBM_TT_THREADS), 0, h->stream, h->dp, h->insts, dt_, dq, dvv, df, dst);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hb + sizeof(double) * B, dq, total - sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+    if (need_legs(h) || use_batch(h)) return -1;
+    const size_t B = h->batch;
+    Carve c;                                          // in: time, q_des (the guess); out: q_des, v_des, force_des, status
+    const auto t = c.add<double>(B), q = c.add<double>(19 * B), v = c.add<double>(18 * B), f = c.add<double>(12 * B);
+    const auto st = c.add<int>(B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(t), time, t.bytes());
+    memcpy(c.host(q), q_des, q.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(t), c.host(t), Carve::span(t, q), hipMemcpyHostToDevice, h->stream));
+    if (srbm_get_targets_from_traj_dev(h, c.dev(t), c.dev(q), c.dev(v), c.dev(f), c.dev(st))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(q), c.dev(q), Carve::span(q, st), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const char* o = hb + sizeof(double) * B;
-    memcpy(q_des, o, sizeof(double) * 19 * B);
-    memcpy(v_des, o + sizeof(double) * 19 * B, sizeof(double) * 18 * B);
-    memcpy(force_des, o + sizeof(double) * 37 * B, sizeof(double) * 12 * B);
-    if (status) memcpy(status, o + sizeof(double) * 49 * B, sizeof(int) * B);
+    memcpy(q_des, c.host(q), q.bytes());
+    memcpy(v_des, c.host(v), v.bytes());
+    memcpy(force_des, c.host(f), f.bytes());
+    if (status) memcpy(status, c.host(st), st.bytes());
     return 0;
 }
 
 // the same on device pointers: one launch on the batch's stream, no copy, no synchronisation (a control tick of the whole batch stays in HBM)
 int srbm_get_targets_from_traj_dev(srbm_batch* h, const double* time_dev, double* q_des_dev, double* v_des_dev, double* force_des_dev, int* status_dev) {
     if (!h || !time_dev || !q_des_dev || !v_des_dev || !force_des_dev || !status_dev) return fail("bad arguments");
-    if (need_legs(h)) return -1;
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (need_legs(h) || use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_targets_from_traj, dim3(h->batch), dim3(SRBM_TT_THREADS), 0, h->stream, h->dp, h->insts, time_dev, q_des_dev, v_des_dev, force_des_dev, status_dev);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1928,43 +1500,31 @@ int srbm_qp_control(srbm_batch* h, const double* q, const double* v, const int* 
     if (!h || !q || !v || !contact || !q_des || !v_des || !force_des || !control) return fail("bad arguments");
     if (need_legs(h)) return -1;
     if (!h->d_wbc) return fail("the whole-body model has not been set (srbm_set_wbc_model)");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     const size_t B = h->batch, DUMP = WBC_MMAX * WBC_NMAX + 2 * WBC_MMAX + 2 * WBC_NMAX;
-    // layout (device = pinned host): inputs [q 19 | v 18 | q_des 19 | v_des 18 | force_des 12] doubles, contact 4 ints (padded to doubles);
-    // outputs [control 36 | qp_sol 30] doubles, status 1 int (padded), then the optional dump
-    const size_t n_in_d = (19 + 18 + 19 + 18 + 12) * B, n_con_d = (4 * B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
-    const size_t n_out_d = (36 + WBC_NMAX) * B, n_st_d = (B * sizeof(int) + sizeof(double) - 1) / sizeof(double);
-    const size_t nd = n_in_d + n_con_d + n_out_d + n_st_d + (qp_dump ? DUMP * B : 0);
-    void *dv = nullptr, *hv = nullptr;
-    if (batch_stage(h, sizeof(double) * nd, &dv, &hv)) return -1;
-    double* dq = static_cast<double*>(dv);
-    double* dvl = dq + 19 * B;
-    double* dqd = dvl + 18 * B;
-    double* dvd = dqd + 19 * B;
-    double* dfd = dvd + 18 * B;
-    int* dcon = reinterpret_cast<int*>(dq + n_in_d);
-    double* dctl = dq + n_in_d + n_con_d;
-    double* dsol = dctl + 36 * B;
-    int* dst = reinterpret_cast<int*>(dctl + n_out_d);
-    double* ddump = qp_dump ? dctl + n_out_d + n_st_d : nullptr;
-    double* hb = static_cast<double*>(hv);
-    memcpy(hb, q, sizeof(double) * 19 * B);
-    memcpy(hb + 19 * B, v, sizeof(double) * 18 * B);
-    memcpy(hb + 37 * B, q_des, sizeof(double) * 19 * B);
-    memcpy(hb + 56 * B, v_des, sizeof(double) * 18 * B);
-    memcpy(hb + 74 * B, force_des, sizeof(double) * 12 * B);
-    memcpy(hb + n_in_d, contact, sizeof(int) * 4 * B);
-    HIPCHK(hipMemcpyAsync(dv, hb, sizeof(double) * (n_in_d + n_con_d), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(srbm_k_qp_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, dq, dvl, dcon, dqd, dvd, dfd, dctl, dsol, dst, ddump);
+    Carve c;                                          // in: q, v, q_des, v_des, force_des, contact; out: control, qp_sol, status, the optional dump
+    const auto iq = c.add<double>(19 * B), iv = c.add<double>(18 * B), iqd = c.add<double>(19 * B), ivd = c.add<double>(18 * B), ifd = c.add<double>(12 * B);
+    const auto icon = c.add<int>(4 * B);
+    const auto oc = c.add<double>(36 * B), os = c.add<double>(WBC_NMAX * B);
+    const auto ost = c.add<int>(B);
+    const auto od = c.add<double>(qp_dump ? DUMP * B : 0);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(iq), q, iq.bytes());
+    memcpy(c.host(iv), v, iv.bytes());
+    memcpy(c.host(iqd), q_des, iqd.bytes());
+    memcpy(c.host(ivd), v_des, ivd.bytes());
+    memcpy(c.host(ifd), force_des, ifd.bytes());
+    memcpy(c.host(icon), contact, icon.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(iq), c.host(iq), Carve::span(iq, icon), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(srbm_k_qp_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, c.dev(iq), c.dev(iv), c.dev(icon), c.dev(iqd),
+                       c.dev(ivd), c.dev(ifd), c.dev(oc), c.dev(os), c.dev(ost), qp_dump ? c.dev(od) : nullptr);
     HIPCHK(hipGetLastError());
-    double* ho = hb + n_in_d + n_con_d;
-    HIPCHK(hipMemcpyAsync(ho, dctl, sizeof(double) * (nd - n_in_d - n_con_d), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(c.host(oc), c.dev(oc), Carve::span(oc, od), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(control, ho, sizeof(double) * 36 * B);
-    if (qp_sol) memcpy(qp_sol, ho + 36 * B, sizeof(double) * WBC_NMAX * B);
-    if (status) memcpy(status, ho + n_out_d, sizeof(int) * B);
-    if (qp_dump) memcpy(qp_dump, ho + n_out_d + n_st_d, sizeof(double) * DUMP * B);
+    memcpy(control, c.host(oc), oc.bytes());
+    if (qp_sol) memcpy(qp_sol, c.host(os), os.bytes());
+    if (status) memcpy(status, c.host(ost), ost.bytes());
+    if (qp_dump) memcpy(qp_dump, c.host(od), od.bytes());
     return 0;
 }
 
@@ -1973,8 +1533,7 @@ int srbm_qp_control_dev(srbm_batch* h, const double* q_dev, const double* v_dev,
     if (!h || !q_dev || !v_dev || !contact_dev || !q_des_dev || !v_des_dev || !force_des_dev || !control_dev || !qp_sol_dev || !status_dev) return fail("bad arguments");
     if (need_legs(h)) return -1;
     if (!h->d_wbc) return fail("the whole-body model has not been set (srbm_set_wbc_model)");
-    HIPCHK(hipSetDevice(h->device));
-    if (upload_params(h)) return -1;
+    if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_qp_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, q_dev, v_dev, contact_dev, q_des_dev, v_des_dev,
                        force_des_dev, control_dev, qp_sol_dev, status_dev, static_cast<double*>(nullptr));
     HIPCHK(hipGetLastError());
