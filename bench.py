@@ -8,9 +8,13 @@ RTI steps with t_i = i*dt and state := node 1 of the previous trajectory (test/g
 (inputs are in HBM when a region starts), in `--repeats` consecutive timed regions of K / repeats steps, each closed by the
 all-gather of the result records.  With the defaults that is BASELINE.md section 3.3's 10 cold starts then 100 CONSECUTIVE timed
 steps, as one region; `value` = instances x steps / SUM of the regions and `ms_per_step` = SUM of the regions / steps -- the
-transient after the cold start included (the median region and the settled rate stand beside it, named as such).  One "step" =
+transient after the cold start included (the median region, and with --full the settled rate, stand beside it, named as such).  One "step" =
 one RTI iteration of every instance of the batch (shift -> assemble -> condense -> QP solve -> line search -> trajectory update).
 `--dump-outputs DIR` writes the gathered result records of the last timed step as DIR/<name>.npy (float64), for comparing builds.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed regions, the dump, and the line with `roofline` (taken from the
+timed launches themselves).  `--full` adds everything that takes runs of its own: the two other solver modes (and `one_region`), Config D
+and E, the gait, closed-loop and control-tick segments, `steady_state` and the CPU baseline, each still skipped by its own option.
 
 Solver mode of the headline (`--mode`, default `lower_start`): EVERY solve ends by the reference's termination test (Clarabel's
 gap 1e-15 / feasibility 1e-10, clarabel_interface.cpp:165-175); in the K-step launches a solve is first attempted from the
@@ -238,6 +242,9 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write the result records of the last timed step of the headline (status header, primal, dual, contact times) as DIR/<name>.npy')
     ap.add_argument('--batch', type=int, default=BATCH_PER_GPU, help='instances per GPU')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need (off by default): the other solver modes, Config D / E, the gait, closed-loop and '
+                         'control-tick segments, the steady-state regions and the CPU baseline; the options below select among them')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--workload', choices=['B', 'D', 'E'], default='B',
                     help='B (default, the metric\'s configuration): 256 instances/GPU, N=20; D: 512 instances/GPU, N=50, push distribution; '
@@ -268,6 +275,9 @@ def main():
     if args.steps % args.repeats:
         raise SystemExit('bench.py: --repeats must divide --steps')
     region_steps = args.steps // args.repeats                 # RTI steps of one timed region (one launch of the fused kernel)
+    if not args.full:        # a plain run: no segment beyond the headline's own protocol
+        args.no_other_modes, args.extra_workloads, args.no_cpu_baseline = True, 0, True
+        args.gait_steps = args.closed_loop_steps = args.wbc_ticks = args.steady_from = 0
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args))

@@ -7,7 +7,7 @@ mkdir -p $D
 export TMPDIR=/tmp
 timeout -k 10 240 python -m pytest tests/test_gpu_wbc.py tests/test_gpu_ik.py -q -s -x > $D/f3_tests.log 2>&1 < /dev/null
 echo "tests rc=$?"; tail -3 $D/f3_tests.log; grep -a "IPM iterations" $D/f3_tests.log | head -1
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $D/trace_f3 -o trace --output-format csv -- python3 bench.py --no-cpu-baseline --no-reference-criterion --extra-workloads 0 --gait-steps 0 --closed-loop-steps 0 --steady-from 0 > $D/bench_f3.json 2> $D/bench_f3.err < /dev/null
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $D/trace_f3 -o trace --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-reference-criterion --extra-workloads 0 --gait-steps 0 --closed-loop-steps 0 --steady-from 0 > $D/bench_f3.json 2> $D/bench_f3.err < /dev/null
 echo "bench rc=$?"
 python3 - $D <<'PY'
 import json, sys, glob, csv

@@ -93,7 +93,7 @@ def counters(sub):
 
 F, W, S1, S2 = counters('pmc_fetch'), counters('pmc_write'), counters('pmc_sq1'), counters('pmc_sq2')
 summ = {'kernel': KERNEL, 'round': rnd, 'kernel_source_sha': bench.kernel_source_sha(), 'steps_per_launch': steps, 'timed_launches': repeats,
-        'command': 'rocprofv3 --pmc <one pass per counter group, no other tracing> -- python3 bench.py --no-cpu-baseline --no-reference-criterion --extra-workloads 0 --gait-steps 0 --closed-loop-steps 0 --wbc-ticks 0',
+        'command': 'rocprofv3 --pmc <one pass per counter group, no other tracing> -- python3 bench.py --full --no-cpu-baseline --no-reference-criterion --extra-workloads 0 --gait-steps 0 --closed-loop-steps 0 --wbc-ticks 0',
         'launch_described': 'mean over the %d timed launches (one per region): counters, duration and the roofline object of the bench line all refer to it' % len(ms),
         'kernel_trace_ms_per_launch': sum(ms) / len(ms), 'kernel_trace_ms_each': ms, 'hip_event_ms_per_launch_same_run': pb['roofline']['avg_launch_ms'],
         'raw_counters_per_launch': {**F, **W, **S1, **S2}}
@@ -140,7 +140,7 @@ def kernel_stats(sub, out_name, title, bench_json=None):
 
 kernel_stats('trace_D', 'D_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats -- python3 bench.py --workload D --no-cpu-baseline --closed-loop-steps 0 (512 instances, N = 50: standard kernel set, two rounds of 256 workgroups)', 'bench_D_under_rocprof.json')
 kernel_stats('trace_E', 'E_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats -- python3 bench.py --workload E --no-cpu-baseline --closed-loop-steps 0 (128 instances, N = 40: LARGE build)', 'bench_E_under_rocprof.json')
-kernel_stats('trace_gait', 'gait_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --closed-loop-steps 0 --wbc-ticks 0 (Config B region + the gait segment: 30 steps, 6 gait steps, 6 line searches)', 'bench_gait_under_rocprof.json')
+kernel_stats('trace_gait', 'gait_kernel_stats.csv', 'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --closed-loop-steps 0 --wbc-ticks 0 (Config B region + the gait segment: 30 steps, 6 gait steps, 6 line searches)', 'bench_gait_under_rocprof.json')
 
 
 def counters_of(sub, kernel_sub):

@@ -25,7 +25,7 @@ def test_bench_line_under_torchrun_with_the_collective_path(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', str(free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2', '--repeats', '2', '--gait-steps', '10', '--closed-loop-steps', '4', '--wbc-ticks', '3',
-           '--dump-outputs', str(tmp_path / 'out')]
+           '--full', '--dump-outputs', str(tmp_path / 'out')]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -80,6 +80,20 @@ def run_bench(*args):
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_plain_run_times_the_headline_alone(tmp_path):
+    """bench.py without --full: the headline's protocol and nothing that takes runs of its own -- the line keeps the measurement contract and
+    the roofline of the timed launches, and --dump-outputs writes the same five arrays"""
+    d = run_bench('--gpus', '1', '--steps', '4', '--warmup', '1', '--dump-outputs', str(tmp_path / 'out'))
+    for k in ('metric', 'value', 'unit', 'ms_per_step', 'higher_is_better', 'dtype', 'config', 'roofline', 'median_region'):
+        assert k in d, k
+    for k in ('reference_criterion', 'reference_criterion_lower_start', 'step_rule_mode', 'one_region', 'config_d', 'config_e', 'steady_state', 'gait',
+              'closed_loop', 'wbc', 'cpu_baseline'):
+        assert k not in d, k
+    assert d['steps'] == 4 and d['warmup'] == 1 and d['solver_mode'] == 'lower_start' and abs(d['value'] - 256 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    assert d['config']['timed_solves'] == 256 * 4 and d['config']['err_bits_all_timed_steps'] == 0 and d['roofline']['launches_timed'] >= 1
+    assert sorted(f[:-4] for f in os.listdir(str(tmp_path / 'out'))) == ['contact_times', 'dual', 'instance', 'primal', 'record_header']
 
 
 def test_config_d_full_per_gpu_share_through_the_bench():
