@@ -38,10 +38,22 @@ struct DevTemps {
     }
 };
 
+// The fields of SrbmParams that belong to ONE instance: its constructor data (srbm_batch_create_each) and its costs (the cost setters).  Every other
+// field of a record is batch-wide: the same in all records, taken from srbm_batch::hp.
+struct InstModel {
+    double mu_fric, force_bound, force_cost, box0[2];
+    double mass, Ir[9], Ir_inv[9];
+    double Q[144], w[12], Phi[144], Phi_w[12];
+};
+
 struct srbm_batch {
     int batch = 0, device = 0;
-    SrbmParams hp{};                 // host copy of the parameters
-    SrbmParams* dp = nullptr;
+    SrbmParams hp{};                 // host copy of the batch-wide parameters (its per-instance fields are not used: see im)
+    std::vector<InstModel> im;       // per-instance parameters [batch]
+    double hip_xy[8] = {};           // srbm_model::hip_xy as given at creation (hp.hip holds GetCOMToHip of it)
+    std::vector<SrbmParams> recs;    // host image of dp: hp with instance b's fields laid over it, one record per instance
+    SrbmParams* dp = nullptr;        // [batch] on the device: every kernel reads the record of the instance it works on
+    unsigned params_gen = 0;         // counts the changes of hp / im (the gait's candidate batch re-derives its records when it moves)
     SrbmInst* insts = nullptr;
     SrbmWork* works = nullptr;
     double *d_state = nullptr, *d_time = nullptr, *d_ee = nullptr;
@@ -137,11 +149,28 @@ template <class F> static int each_inst(srbm_batch* h, F f) {
     for (int b = 0; b < h->batch; b++) f(b, v[b]);
     return 0;
 }
+// the record of instance b: the batch-wide fields, then the instance's own
+static SrbmParams inst_params(const srbm_batch* h, int b) {
+    SrbmParams p = h->hp;
+    const InstModel& m = h->im[b];
+    p.mu_fric = m.mu_fric; p.force_bound = m.force_bound; p.force_cost = m.force_cost;
+    p.box0[0] = m.box0[0]; p.box0[1] = m.box0[1];
+    p.mass = m.mass;
+    std::memcpy(p.Ir, m.Ir, sizeof(p.Ir)); std::memcpy(p.Ir_inv, m.Ir_inv, sizeof(p.Ir_inv));
+    std::memcpy(p.Q, m.Q, sizeof(p.Q)); std::memcpy(p.w, m.w, sizeof(p.w));
+    std::memcpy(p.Phi, m.Phi, sizeof(p.Phi)); std::memcpy(p.Phi_w, m.Phi_w, sizeof(p.Phi_w));
+    // per instance: a full Q on one instance sends that instance alone down the 12x12 path of the condensing kernel
+    p.q_diag = 1;
+    for (int i = 0; i < 144; i++) if (i % 13 != 0 && (p.Q[i] != 0.0 || p.Phi[i] != 0.0)) p.q_diag = 0;
+    return p;
+}
+// hp or im changed: the records go to the device before the next launch
+static void params_changed(srbm_batch* h) { h->params_dirty = true; h->params_gen++; }
 static int upload_params(srbm_batch* h) {
     if (!h->params_dirty) return 0;
-    h->hp.q_diag = 1;
-    for (int i = 0; i < 144; i++) if (i % 13 != 0 && (h->hp.Q[i] != 0.0 || h->hp.Phi[i] != 0.0)) h->hp.q_diag = 0;
-    HIPCHK(hipMemcpyAsync(h->dp, &h->hp, sizeof(SrbmParams), hipMemcpyHostToDevice, h->stream));
+    h->recs.resize(h->batch);
+    for (int b = 0; b < h->batch; b++) h->recs[b] = inst_params(h, b);
+    HIPCHK(hipMemcpyAsync(h->dp, h->recs.data(), sizeof(SrbmParams) * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     h->params_dirty = false;
     return 0;
 }
@@ -285,7 +314,7 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     const size_t B = h->batch;
     if (borrowed_stream) { h->stream = borrowed_stream; h->owns_stream = false; }
     else { HIPCHK(hipStreamCreate(&h->stream)); h->owns_stream = true; }
-    HIPCHK(hipMalloc(&h->dp, sizeof(SrbmParams)));
+    HIPCHK(hipMalloc(&h->dp, sizeof(SrbmParams) * B));
     HIPCHK(hipMalloc(&h->insts, sizeof(SrbmInst) * B));
     HIPCHK(hipMalloc(&h->works, sizeof(SrbmWork) * B));
     HIPCHK(hipMalloc(&h->d_state, sizeof(double) * 13 * B));
@@ -311,23 +340,48 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     return 0;
 }
 
-int srbm_batch_create(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, int device) {
-    if (!out || !info || !model || batch <= 0) return fail("srbm_batch_create: bad arguments");
-    if (info->num_nodes < 5 || info->num_nodes > SRBM_NMAX) return fail("srbm_batch_create: num_nodes must be in [5, " + std::to_string(SRBM_NMAX) + "]");
+// The checks of srbm_batch_create / srbm_batch_create_each, before any device is probed (so that they can be tested without a GPU).  each: info and
+// model are arrays [batch], else one record for every instance.  The fields that fix the QP shapes, the LDS map, the time grid and the foot geometry
+// are batch-wide: instances that disagree on one are refused with its name.
+static int check_create(const char* fn, srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, bool each) {
+    if (!out || !info || !model || batch <= 0) return fail(std::string(fn) + ": bad arguments");
+    if (info->num_nodes < 5 || info->num_nodes > SRBM_NMAX) return fail(std::string(fn) + ": num_nodes must be in [5, " + std::to_string(SRBM_NMAX) + "]");
+    for (int b = 1; each && b < batch; b++) {
+        const srbm_mpc_info& a = info[b];
+        const char* field = a.num_nodes != info->num_nodes ? "num_nodes" : a.integrator_dt != info->integrator_dt ? "integrator_dt"
+                          : a.swing_height != info->swing_height ? "swing_height" : a.foot_offset != info->foot_offset ? "foot_offset"
+                          : std::memcmp(model[b].hip_xy, model->hip_xy, sizeof(model->hip_xy)) != 0 ? "hip_xy" : nullptr;
+        if (field) return fail(std::string(fn) + ": instance " + std::to_string(b) + ": " + field + " differs from instance 0 (it is batch-wide: one value "
+                               "for every instance of a batch)");
+    }
+    return 0;
+}
+static void set_inst_model(InstModel& m, const srbm_mpc_info& info, const srbm_model& model) {
+    m.mu_fric = info.friction_coef; m.force_bound = info.force_bound; m.force_cost = info.force_cost;
+    m.box0[0] = info.ee_box_size[0]; m.box0[1] = info.ee_box_size[1];
+    m.mass = model.mass;
+    std::memcpy(m.Ir, model.Ir, sizeof(m.Ir));
+    inv3(m.Ir, m.Ir_inv);
+}
+static int create_batch(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, bool each, int device) {
+    const char* fn = each ? "srbm_batch_create_each" : "srbm_batch_create";
+    if (check_create(fn, out, batch, info, model, each)) return -1;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("srbm_batch_create: no HIP device (this library has no CPU path)");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(std::string(fn) + ": no HIP device (this library has no CPU path)");
     HIPCHK(hipSetDevice(device));
     auto* h = new srbm_batch;
     h->batch = batch; h->device = device;
     SrbmParams& p = h->hp;
     std::memset(&p, 0, sizeof(p));
     p.batch = batch; p.N = info->num_nodes; p.max_iter = 200;
-    p.dt = info->integrator_dt; p.mu_fric = info->friction_coef; p.force_bound = info->force_bound;
-    p.swing_height = info->swing_height; p.foot_offset = info->foot_offset; p.force_cost = info->force_cost;
-    p.box0[0] = info->ee_box_size[0]; p.box0[1] = info->ee_box_size[1];
-    p.mass = model->mass;
-    std::memcpy(p.Ir, model->Ir, sizeof(p.Ir));
-    inv3(p.Ir, p.Ir_inv);
+    p.dt = info->integrator_dt; p.swing_height = info->swing_height; p.foot_offset = info->foot_offset;
+    h->im.resize(batch);
+    for (int b = 0; b < batch; b++) {
+        InstModel& m = h->im[b];
+        std::memset(&m, 0, sizeof(m));
+        set_inst_model(m, info[each ? b : 0], model[each ? b : 0]);
+    }
+    std::memcpy(h->hip_xy, model->hip_xy, sizeof(h->hip_xy));
     for (int ee = 0; ee < 4; ee++) {      // GetCOMToHip, single_rigid_body_model.cpp:289-305
         double x = model->hip_xy[2 * ee], y = model->hip_xy[2 * ee + 1];
         if (y >= 0) y += 0.1; else y -= 0.1;
@@ -345,11 +399,28 @@ int srbm_batch_create(srbm_batch** out, int batch, const srbm_mpc_info* info, co
     p.tol_step = 0.0; p.start_mu = 0.0;       // the reference's criterion; srbm_set_solver_step_rule opts into the faster termination
     auto bail = [&]() { free_batch(h); return -1; };
     if (alloc_batch(h, nullptr)) return bail();
-    if (hipMemsetAsync(h->works, 0, sizeof(SrbmWork) * (size_t)batch, h->stream) != hipSuccess) { fail("srbm_batch_create: memset failed"); return bail(); }
+    if (hipMemsetAsync(h->works, 0, sizeof(SrbmWork) * (size_t)batch, h->stream) != hipSuccess) { fail(std::string(fn) + ": memset failed"); return bail(); }
     if (upload_params(h)) return bail();
     hipLaunchKernelGGL(srbm_k_init, dim3((batch + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_create: initialisation kernel failed"); return bail(); }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { fail(std::string(fn) + ": initialisation kernel failed"); return bail(); }
     *out = h;
+    return 0;
+}
+int srbm_batch_create(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, int device) {
+    return create_batch(out, batch, info, model, false, device);
+}
+int srbm_batch_create_each(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, int device) {
+    return create_batch(out, batch, info, model, true, device);
+}
+int srbm_get_instance_model(const srbm_batch* h, int inst, srbm_mpc_info* info, srbm_model* model) {
+    if (!h || inst < 0 || inst >= h->batch || !info || !model) return fail("srbm_get_instance_model: bad arguments");
+    const InstModel& m = h->im[inst];
+    info->num_nodes = h->hp.N; info->integrator_dt = h->hp.dt; info->friction_coef = m.mu_fric; info->force_bound = m.force_bound;
+    info->swing_height = h->hp.swing_height; info->foot_offset = h->hp.foot_offset;
+    info->ee_box_size[0] = m.box0[0]; info->ee_box_size[1] = m.box0[1]; info->force_cost = m.force_cost;
+    model->mass = m.mass;
+    std::memcpy(model->Ir, m.Ir, sizeof(model->Ir));
+    std::memcpy(model->hip_xy, h->hip_xy, sizeof(model->hip_xy));
     return 0;
 }
 
@@ -359,7 +430,8 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     HIPCHK(hipSetDevice(src->device));
     HIPCHK(hipStreamSynchronize(src->stream));
     auto* h = new srbm_batch;
-    h->batch = src->batch; h->device = src->device; h->hp = src->hp; h->push_set = src->push_set; h->last_tol_step = src->last_tol_step;
+    h->batch = src->batch; h->device = src->device; h->hp = src->hp; h->im = src->im; std::memcpy(h->hip_xy, src->hip_xy, sizeof(h->hip_xy));
+    h->push_set = src->push_set; h->last_tol_step = src->last_tol_step;
     auto bail = [&]() { free_batch(h); return -1; };
     if (alloc_batch(h, nullptr)) return bail();
     const size_t B = h->batch;
@@ -390,46 +462,83 @@ int srbm_batch_destroy(srbm_batch* h) {
     return 0;
 }
 
-int srbm_add_quadratic_tracking_cost(srbm_batch* h, const double* state_des12, const double* Q144) {
-    if (!h || !state_des12 || !Q144) return fail("bad arguments");
-    std::memcpy(h->hp.Q, Q144, sizeof(double) * 144);
+// The cost setters write instances [first, first + count) from arrays [count][...]; the batch-wide entries below write every instance (the last write
+// wins per instance).
+static int check_each(const char* fn, const srbm_batch* h, int first, int count, std::initializer_list<const void*> arrays) {
+    if (!h) return fail(std::string(fn) + ": bad arguments (NULL handle)");
+    if (first < 0 || count < 0 || first > h->batch || count > h->batch - first)
+        return fail(std::string(fn) + ": first / count out of range (first " + std::to_string(first) + ", count " + std::to_string(count) + ", batch " +
+                    std::to_string(h->batch) + ")");
+    for (const void* a : arrays) if (!a) return fail(std::string(fn) + ": bad arguments (NULL array)");
+    return 0;
+}
+static void tracking_cost(InstModel& m, const double* state_des12, const double* Q144) {
+    std::memcpy(m.Q, Q144, sizeof(double) * 144);
     for (int i = 0; i < 12; i++) {
         double a = 0;
         for (int j = 0; j < 12; j++) a += Q144[i * 12 + j] * state_des12[j];
-        h->hp.w[i] = -1 * a;
+        m.w[i] = -1 * a;
     }
-    h->params_dirty = true;
+}
+int srbm_add_quadratic_tracking_cost_each(srbm_batch* h, int first, int count, const double* state_des12, const double* Q144) {
+    if (check_each("srbm_add_quadratic_tracking_cost_each", h, first, count, {state_des12, Q144})) return -1;
+    for (int i = 0; i < count; i++) tracking_cost(h->im[first + i], state_des12 + 12 * i, Q144 + 144 * i);
+    params_changed(h);
+    return 0;
+}
+int srbm_set_quadratic_final_cost_each(srbm_batch* h, int first, int count, const double* Phi144) {
+    if (check_each("srbm_set_quadratic_final_cost_each", h, first, count, {Phi144})) return -1;
+    for (int i = 0; i < count; i++) std::memcpy(h->im[first + i].Phi, Phi144 + 144 * i, sizeof(double) * 144);
+    params_changed(h);
+    return 0;
+}
+int srbm_set_linear_final_cost_each(srbm_batch* h, int first, int count, const double* w12) {
+    if (check_each("srbm_set_linear_final_cost_each", h, first, count, {w12})) return -1;
+    for (int i = 0; i < count; i++) std::memcpy(h->im[first + i].Phi_w, w12 + 12 * i, sizeof(double) * 12);
+    params_changed(h);
+    return 0;
+}
+int srbm_add_force_cost_each(srbm_batch* h, int first, int count, const double* weight) {
+    if (check_each("srbm_add_force_cost_each", h, first, count, {weight})) return -1;
+    for (int i = 0; i < count; i++) h->im[first + i].force_cost = weight[i];
+    params_changed(h);
+    return 0;
+}
+int srbm_add_quadratic_tracking_cost(srbm_batch* h, const double* state_des12, const double* Q144) {
+    if (!h || !state_des12 || !Q144) return fail("bad arguments");
+    for (InstModel& m : h->im) tracking_cost(m, state_des12, Q144);
+    params_changed(h);
     return 0;
 }
 int srbm_set_quadratic_final_cost(srbm_batch* h, const double* Phi144) {
     if (!h || !Phi144) return fail("bad arguments");
-    std::memcpy(h->hp.Phi, Phi144, sizeof(double) * 144);
-    h->params_dirty = true;
+    for (InstModel& m : h->im) std::memcpy(m.Phi, Phi144, sizeof(double) * 144);
+    params_changed(h);
     return 0;
 }
 int srbm_set_linear_final_cost(srbm_batch* h, const double* w12) {
     if (!h || !w12) return fail("bad arguments");
-    std::memcpy(h->hp.Phi_w, w12, sizeof(double) * 12);
-    h->params_dirty = true;
+    for (InstModel& m : h->im) std::memcpy(m.Phi_w, w12, sizeof(double) * 12);
+    params_changed(h);
     return 0;
 }
 // MPC::AddForceCost (mpc.cpp:791-802): weight on every force spline variable
 int srbm_add_force_cost(srbm_batch* h, double weight) {
     if (!h) return fail("bad arguments");
-    h->hp.force_cost = weight;
-    h->params_dirty = true;
+    for (InstModel& m : h->im) m.force_cost = weight;
+    params_changed(h);
     return 0;
 }
 int srbm_set_solver_tolerances(srbm_batch* h, double ga, double gr, double tf, int max_iter) {
     if (!h) return fail("bad arguments");
     h->hp.tol_gap_abs = ga; h->hp.tol_gap_rel = gr; h->hp.tol_feas = tf; h->hp.max_iter = max_iter;
-    h->params_dirty = true;
+    params_changed(h);
     return 0;
 }
 int srbm_set_solver_step_rule(srbm_batch* h, double tol_step, double start_mu) {
     if (!h || !(tol_step >= 0.0) || !(start_mu >= 0.0)) return fail("bad arguments");
     h->hp.tol_step = tol_step; h->hp.start_mu = start_mu;
-    h->params_dirty = true;
+    params_changed(h);
     return 0;
 }
 int srbm_get_solver_step_rule(const srbm_batch* h, double* tol_step, double* start_mu) {
@@ -607,12 +716,21 @@ struct srbm_gait {
     double* pred_red = nullptr;                                                   // [B]
     int* ready = nullptr;                                                         // [B] deriv_ready of the controller
     SrbmGaitWork* gw = nullptr;                                                   // sensitivity workspace, one per instance
+    unsigned ls_gen = 0;                                                          // params_gen of h the candidates' records were derived from
 };
+
+// the parameters of the candidate batch: candidate w = b * LS_SIZE + c solves with instance b's record
+static void candidate_params(const srbm_batch* h, srbm_batch* c) {
+    c->hp = h->hp; c->hp.batch = c->batch;
+    c->im.resize(c->batch);
+    for (int w = 0; w < c->batch; w++) c->im[w] = h->im[w / SRBM_LS_SIZE];
+    c->params_dirty = true;
+}
 
 static int make_candidate_batch(const srbm_batch* h, srbm_batch** out) {
     auto* c = new srbm_batch;
     c->batch = h->batch * SRBM_LS_SIZE; c->device = h->device;
-    c->hp = h->hp; c->hp.batch = c->batch;
+    candidate_params(h, c);
     if (alloc_batch(c, h->stream) || hipMemsetAsync(c->works, 0, sizeof(SrbmWork) * (size_t)c->batch, c->stream) != hipSuccess) {
         free_batch(c);
         return g_err.empty() ? fail("candidate batch: allocation failed") : -1;
@@ -634,6 +752,7 @@ static void free_gait(srbm_gait* g) {
 static int alloc_gait(srbm_gait* g) {
     srbm_batch* h = g->h;
     if (make_candidate_batch(h, &g->ls)) return -1;
+    g->ls_gen = h->params_gen;
     const size_t B = h->batch;
     HIPCHK(hipMalloc(&g->xk, sizeof(double) * SRBM_GAIT_NV * B));
     HIPCHK(hipMalloc(&g->step, sizeof(double) * SRBM_GAIT_NV * B));
@@ -738,7 +857,7 @@ int srbm_gait_get_param_partials(srbm_batch* h, int inst, int ee, int idx, doubl
     HIPCHK(tmp.alloc(&d, sizeof(double) * tot));
     HIPCHK(hipMemsetAsync(d, 0, sizeof(double) * tot, h->stream));
     int* derr = reinterpret_cast<int*>(d + me * n + mi * n + me);
-    hipLaunchKernelGGL(srbm_k_gait_param_partials, dim3(1), dim3(KH_THREADS), 0, h->stream, h->dp, h->insts + inst, h->works + inst, ee, idx,
+    hipLaunchKernelGGL(srbm_k_gait_param_partials, dim3(1), dim3(KH_THREADS), 0, h->stream, h->dp + inst, h->insts + inst, h->works + inst, ee, idx,
                        d, d + me * n, d + me * n + mi * n, derr);
     HIPCHK(hipGetLastError());
     int err = 0;
@@ -798,7 +917,7 @@ static int line_search_core(srbm_gait* g, bool use_ready_mask) {
     srbm_batch* h = g->h; srbm_batch* ls = g->ls;
     const int B = h->batch;
     if (upload_params(h)) return -1;
-    ls->hp = h->hp; ls->hp.batch = ls->batch; ls->params_dirty = true;      // costs / tolerances may have changed since creation
+    if (g->ls_gen != h->params_gen) { candidate_params(h, ls); g->ls_gen = h->params_gen; }     // costs / tolerances changed since the last line search
     if (upload_params(ls)) return -1;
     const int* ready = use_ready_mask ? g->ready : nullptr;
     hipLaunchKernelGGL(srbm_k_gait_spawn_candidates, dim3(B * SRBM_LS_SIZE), dim3(128), 0, h->stream, h->dp, h->insts, ls->insts,
@@ -1108,7 +1227,7 @@ int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* Pm, do
     if (fetch(h, {{vi.data(), h->insts + inst, sizeof(SrbmInst)}, {vw.data(), h->works + inst, sizeof(SrbmWork)}})) return -1;
     const SrbmInst& I = vi[0];
     const SrbmWork& W = vw[0];
-    const SrbmParams& P = h->hp;
+    const SrbmParams P = inst_params(h, inst);
     const int N = P.N, n = I.n, m = I.m, nx = (N + 1) * 12, ns = W.n_samp;
     const double dt = P.dt;
     if (A) std::memset(A, 0, sizeof(double) * (size_t)m * n);
@@ -1413,7 +1532,7 @@ int srbm_set_leg_kinematics(srbm_batch* h, const srbm_leg_kinematics* legs) {
     if (!h || !legs) return fail("bad arguments");
     std::memcpy(h->hp.legs, legs->origin, sizeof(h->hp.legs));
     h->hp.has_legs = 1;
-    h->params_dirty = true;
+    params_changed(h);
     return 0;
 }
 static int need_legs(srbm_batch* h) { return h->hp.has_legs ? 0 : fail("the leg geometry has not been set (srbm_set_leg_kinematics)"); }

@@ -56,6 +56,8 @@ enum { SRBM_ERR_TIME_SMALL = 1, SRBM_ERR_TIME_LARGE = 2, SRBM_ERR_INVALID_TIME =
        SRBM_ERR_STRUCTURE = 256 /* internal invariant: a dense state row has a non-zero outside the force variables of its coordinate (srbm_k2_condense.hiph) */,
        SRBM_ERR_QUEUE = 512 /* a bounded wait of the step queue of a batch larger than the chip ran out (srbm_fused.hiph: srbm_rti_queued) */ };
 
+/* One record per instance (srbm_capi.hip uploads dp[batch]): mass, Ir, Ir_inv, mu_fric, force_bound, force_cost, box0, Q, w, Phi, Phi_w and q_diag
+   are the instance's own; every other field is batch-wide and the same in every record.  A kernel reads the record of the instance it works on. */
 typedef struct SrbmParams {
     int batch, N;
     int max_iter, lds_doubles;      /* IPM iteration limit; doubles of dynamic LDS the IPM kernel is launched with */

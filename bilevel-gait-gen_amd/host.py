@@ -183,10 +183,46 @@ def manifold_to_tangent(s13):
     return t
 
 
+def _info_model(cfg):
+    """the constructor data of one reference object: (srbm_mpc_info, srbm_model) of a cfg dict"""
+    info = MPCInfo()
+    info.num_nodes = int(cfg['num_nodes'])
+    info.integrator_dt = cfg['integrator_dt']
+    info.friction_coef = cfg['friction_coef']
+    info.force_bound = cfg['force_bound']
+    info.swing_height = cfg['swing_height']
+    info.foot_offset = cfg['foot_offset']
+    info.ee_box_size[:] = [float(v) for v in cfg['ee_box_size']]
+    info.force_cost = cfg['force_cost']
+    model = Model()
+    model.mass = cfg['mass']
+    model.Ir[:] = list(np.asarray(cfg['Ir'], float).reshape(-1))
+    model.hip_xy[:] = list(np.asarray(cfg['hip_xy'], float).reshape(-1))
+    return info, model
+
+
+def _tracking_cost(cfg):
+    """(Q, state_des) of the caller's cost set-up: /root/reference/controllers/mpc_controller.cpp:57-67"""
+    return np.diag(np.asarray(cfg['Q_srbd_diag'], float)), manifold_to_tangent(cfg['srb_target'])
+
+
+# keys of a cfg that are one value for the whole batch (srbm_batch_create_each; the leg kinematics and the whole-body QP model are batch-wide setters)
+BATCH_WIDE_KEYS = ('num_nodes', 'integrator_dt', 'swing_height', 'foot_offset', 'hip_xy', 'large', 'leg_origins', 'body_model', 'torque_bounds',
+                   'kp_joint_gains', 'kd_joint_gains', 'base_pos_gains', 'base_ang_gains', 'leg_tracking_weight', 'torso_tracking_weight',
+                   'force_tracking_weight')
+
+
+def _same(a, b):
+    try:
+        return np.array_equal(np.asarray(a, float), np.asarray(b, float))
+    except (TypeError, ValueError):
+        return a == b
+
+
 class BatchMPC:
     """batch x mpc::MPCSingleRigidBody on one MI355X."""
 
-    def __init__(self, cfg, batch, device=0, large=None):
+    def __init__(self, cfg, batch, device=0, large=None, _cfgs=None):
         self.N = int(cfg['num_nodes'])
         # horizons beyond the standard build's 50 nodes (or an explicit request) go to the LARGE-capacity build
         self.large = bool(cfg.get('large', self.N > lib().capacity['N'])) if large is None else bool(large)
@@ -194,27 +230,23 @@ class BatchMPC:
         self.NUMAX, self.NSMAX = self.L.capacity['nu'], self.L.capacity['samples']
         self.cfg = cfg
         self.batch = int(batch)
-        info = MPCInfo()
-        info.num_nodes = self.N
-        info.integrator_dt = cfg['integrator_dt']
-        info.friction_coef = cfg['friction_coef']
-        info.force_bound = cfg['force_bound']
-        info.swing_height = cfg['swing_height']
-        info.foot_offset = cfg['foot_offset']
-        info.ee_box_size[:] = [float(v) for v in cfg['ee_box_size']]
-        info.force_cost = cfg['force_cost']
-        model = Model()
-        model.mass = cfg['mass']
-        model.Ir[:] = list(np.asarray(cfg['Ir'], float).reshape(-1))
-        model.hip_xy[:] = list(np.asarray(cfg['hip_xy'], float).reshape(-1))
         self.h = C.c_void_p()
-        self._chk(self.L.srbm_batch_create(C.byref(self.h), self.batch, C.byref(info), C.byref(model), int(device)))
-        # cost set-up exactly as the caller does it: /root/reference/controllers/mpc_controller.cpp:57-67
-        Q = np.diag(np.asarray(cfg['Q_srbd_diag'], float))
-        des = manifold_to_tangent(cfg['srb_target'])
-        self.add_quadratic_tracking_cost(des, Q)
-        self.set_quadratic_final_cost(Q)
-        self.set_linear_final_cost(-1 * Q @ des)
+        if _cfgs is None:
+            info, model = _info_model(cfg)
+            self._chk(self.L.srbm_batch_create(C.byref(self.h), self.batch, C.byref(info), C.byref(model), int(device)))
+            Q, des = _tracking_cost(cfg)
+            self.add_quadratic_tracking_cost(des, Q)
+            self.set_quadratic_final_cost(Q)
+            self.set_linear_final_cost(-1 * Q @ des)
+        else:
+            im = [_info_model(c) for c in _cfgs]
+            infos = (MPCInfo * self.batch)(*[i for i, _ in im]); models = (Model * self.batch)(*[m for _, m in im])
+            self._chk(self.L.srbm_batch_create_each(C.byref(self.h), self.batch, infos, models, int(device)))
+            qd = [_tracking_cost(c) for c in _cfgs]
+            Q = np.stack([q for q, _ in qd]); des = np.stack([d for _, d in qd])
+            self.add_quadratic_tracking_cost_each(0, des, Q)
+            self.set_quadratic_final_cost_each(0, Q)
+            self.set_linear_final_cost_each(0, np.stack([-1 * q @ d for q, d in qd]))      # (the expression of the uniform path, per instance)
         if 'leg_origins' in cfg:            # leg geometry for the whole-body targets (row f3)
             lo = np.ascontiguousarray(cfg['leg_origins'], dtype=np.float64).reshape(4, 4, 3)
             self._chk(self.L.srbm_set_leg_kinematics(self.h, _d(lo)))
@@ -230,6 +262,28 @@ class BatchMPC:
             w.leg_tracking_weight = cfg['leg_tracking_weight']; w.torso_tracking_weight = cfg['torso_tracking_weight']
             w.force_tracking_weight = cfg['force_tracking_weight']; w.friction_coef = cfg['friction_coef']; w.max_grf = cfg['force_bound']
             self._chk(self.L.srbm_set_wbc_model(self.h, C.byref(w)))
+
+    @classmethod
+    def from_configs(cls, cfgs, device=0, large=None):
+        """One instance per cfg dict, each its own reference object: its own MPCInfo, mass and inertia (srbm_batch_create_each) and its own
+        tracking cost from its Q_srbd_diag / srb_target, set up as BatchMPC(cfg, 1) sets it (mpc_controller.cpp:57-67).  The horizon, the time step,
+        the foot geometry, the leg kinematics and the whole-body QP model (set from config 0) are batch-wide: configs that differ in one raise
+        ValueError before the library is called."""
+        cfgs = list(cfgs)
+        if not cfgs:
+            raise ValueError('from_configs: no configs')
+        c0 = cfgs[0]
+        for i, c in enumerate(cfgs[1:], 1):
+            for k in BATCH_WIDE_KEYS:
+                if (k in c) != (k in c0) or (k in c and not _same(c[k], c0[k])):
+                    raise ValueError('from_configs: config %d: %s differs from config 0 (it is batch-wide: one value for every instance)' % (i, k))
+        return cls(c0, len(cfgs), device=device, large=large, _cfgs=cfgs)
+
+    def instance_model(self, inst):
+        """srbm_get_instance_model: (srbm_mpc_info, srbm_model) of instance inst"""
+        info = MPCInfo(); model = Model()
+        self._chk(self.L.srbm_get_instance_model(self.h, int(inst), C.byref(info), C.byref(model)))
+        return info, model
 
     def close(self):
         """srbm_batch_destroy.  A batch that gait handles still borrow is NOT released by the library (return code -1): the handle is kept, so that
@@ -334,6 +388,26 @@ class BatchMPC:
     def set_linear_final_cost(self, w):
         a = np.ascontiguousarray(w, dtype=np.float64)
         self._chk(self.L.srbm_set_linear_final_cost(self.h, _d(a)))
+
+    # the cost setters of instances [first, first + len(...)): one row per instance
+    def add_quadratic_tracking_cost_each(self, first, state_des, Q):
+        a = np.ascontiguousarray(state_des, dtype=np.float64).reshape(-1, 12)
+        q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, 144)
+        if len(a) != len(q):
+            raise ValueError('add_quadratic_tracking_cost_each: %d targets, %d weight matrices' % (len(a), len(q)))
+        self._chk(self.L.srbm_add_quadratic_tracking_cost_each(self.h, int(first), len(a), _d(a), _d(q)))
+
+    def set_quadratic_final_cost_each(self, first, Phi):
+        q = np.ascontiguousarray(Phi, dtype=np.float64).reshape(-1, 144)
+        self._chk(self.L.srbm_set_quadratic_final_cost_each(self.h, int(first), len(q), _d(q)))
+
+    def set_linear_final_cost_each(self, first, w):
+        a = np.ascontiguousarray(w, dtype=np.float64).reshape(-1, 12)
+        self._chk(self.L.srbm_set_linear_final_cost_each(self.h, int(first), len(a), _d(a)))
+
+    def add_force_cost_each(self, first, weight):
+        a = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        self._chk(self.L.srbm_add_force_cost_each(self.h, int(first), len(a), _d(a)))
 
     def set_solver_step_rule(self, tol_step, start_mu=0.0):
         self._chk(self.L.srbm_set_solver_step_rule(self.h, C.c_double(tol_step), C.c_double(start_mu)))

@@ -54,3 +54,26 @@ def config_d_instance(cfg, b):
     state[12] += rng.normal(0.0, 0.2)
     ee = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)      # test/simulation_mpc.cpp:104-108
     return state, ee
+
+
+def heterogeneous_configs(base, q_diags, B, seed=4242, num_nodes=None):
+    """B configs around `base` that differ in every per-instance field of the batch (srbm_batch_create_each, BatchMPC.from_configs): mass
+    +-15 %, Ir scaled by 0.8 .. 1.2, friction 0.5 / 0.6, force bound 150 / 200, force cost 0 / 1e-3, a Q diagonal drawn from q_diags, a
+    target with x, y in [0, 1] and height 0.28 .. 0.34.  The batch-wide fields (horizon, time step, foot geometry) are base's."""
+    rng = np.random.Generator(np.random.MT19937(seed))
+    cfgs = []
+    for b in range(B):
+        c = dict(base)
+        if num_nodes is not None:
+            c['num_nodes'] = num_nodes
+        c['mass'] = base['mass'] * (1 + rng.uniform(-0.15, 0.15))
+        c['Ir'] = (np.asarray(base['Ir'], float) * rng.uniform(0.8, 1.2)).tolist()
+        c['friction_coef'] = (0.5, 0.6)[b % 2]
+        c['force_bound'] = (150.0, 200.0)[(b // 2) % 2]
+        c['force_cost'] = (0.0, 1e-3)[(b // 4) % 2]
+        c['Q_srbd_diag'] = list(q_diags[int(rng.integers(len(q_diags)))])
+        tgt = list(base['srb_target'])
+        tgt[0], tgt[1], tgt[2] = rng.uniform(0, 1), rng.uniform(0, 1), rng.uniform(0.28, 0.34)
+        c['srb_target'] = tgt
+        cfgs.append(c)
+    return cfgs

@@ -2,8 +2,9 @@
  *
  * Every entry point replaces, for a BATCH of independent MPC instances, one public method of the reference's
  * mpc::MPC / mpc::MPCSingleRigidBody (cited per function, paths relative to /root/reference).  Instance b of the batch
- * is exactly one reference object: same constructor arguments (srbm_mpc_info + model constants), same default contact
- * schedule, same state.  Plain pointers and sizes only; all array arguments are HOST pointers unless the function
+ * is exactly one reference object: its constructor arguments (srbm_mpc_info + model constants: one set for every instance
+ * through srbm_batch_create, one per instance through srbm_batch_create_each), its costs, the default contact schedule,
+ * its state.  Plain pointers and sizes only; all array arguments are HOST pointers unless the function
  * name ends in _dev.  Return value: 0 on success, negative on error (srbm_last_error() gives the text).
  * The library fails loudly: there is no CPU fallback of any kind.
  */
@@ -33,6 +34,13 @@ typedef struct srbm_model {
 
 /* MPCSingleRigidBody::MPCSingleRigidBody x batch  (mpc/mpc_single_rigid_body.cpp:9-23, mpc/mpc.cpp:38-76) */
 int srbm_batch_create(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, int device);
+/* batch x MPCSingleRigidBody::MPCSingleRigidBody, each with its own constructor data: info[batch], model[batch].  Per instance: mass, Ir,
+ * friction_coef, force_bound, force_cost, ee_box_size.  Batch-wide -- they fix the QP shapes, the time grid and the foot geometry --:
+ * num_nodes, integrator_dt, swing_height, foot_offset and hip_xy; instances that disagree on one are refused with an error that names it
+ * (checked before any device is probed).  The cost setters below then write every instance, their _each forms a range of instances. */
+int srbm_batch_create_each(srbm_batch** out, int batch, const srbm_mpc_info* info, const srbm_model* model, int device);
+/* read-back of instance inst's constructor data (force_cost: as last set by srbm_add_force_cost[_each]) */
+int srbm_get_instance_model(const srbm_batch* h, int inst, srbm_mpc_info* info, srbm_model* model);
 int srbm_batch_destroy(srbm_batch* h);
 const char* srbm_last_error(void);
 
@@ -55,6 +63,13 @@ int srbm_set_quadratic_final_cost(srbm_batch* h, const double* Phi144);
 int srbm_set_linear_final_cost(srbm_batch* h, const double* w12);
 /* MPC::AddForceCost (mpc/mpc.cpp:791-802): weight of every force spline variable (replaces srbm_mpc_info.force_cost) */
 int srbm_add_force_cost(srbm_batch* h, double weight);
+/* The four cost setters above write EVERY instance (the last write wins per instance).  Their _each forms are the same methods of the reference
+ * objects [first, first + count) of the batch, one call per object folded into one: arrays [count][...] (state_des12 [count][12], Q144 and
+ * Phi144 [count][144], w12 [count][12], weight [count]).  first / count out of range or a NULL array: error, the batch unchanged. */
+int srbm_add_quadratic_tracking_cost_each(srbm_batch* h, int first, int count, const double* state_des12, const double* Q144);
+int srbm_set_quadratic_final_cost_each(srbm_batch* h, int first, int count, const double* Phi144);
+int srbm_set_linear_final_cost_each(srbm_batch* h, int first, int count, const double* w12);
+int srbm_add_force_cost_each(srbm_batch* h, int first, int count, const double* weight);
 /* MPC::SetStateTrajectoryWarmStart (mpc/mpc.cpp:700-706): states[batch][13], replicated over the horizon */
 int srbm_set_state_trajectory_warm_start(srbm_batch* h, const double* states);
 /* ClarabelInterface tolerances (mpc/qp/clarabel_interface.cpp:18-27,165-175) for the on-device IPM.
