@@ -239,44 +239,75 @@ int srbm_debug_get_profile2(srbm_batch* h, int inst, double* out96) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
     return fetch(h, {{out96, work_field(h, inst, offsetof(SrbmWork, prof2)), sizeof(double) * 96}});
 }
-int srbm_debug_solve_mapped(int n, int nc, const int* map, int count, const double* M_packed, const double* rhs, double* x, int* nreg) {
-#ifdef SRBM_LARGE
-    return fail("srbm_debug_solve_mapped: the unit-test hooks of the dense blocks exist in the standard build only");
+/* unit-test hooks of the dense blocks (srbm_dense_hooks.hiph), in both builds: the packed matrices where the IPM keeps its normal matrix -- the
+   LDS (standard build) or, SRBM_M_GLOBAL, a device workspace of one slice per matrix with DBG_PAD doubles after each --; `fill` is written to
+   the doubles after each packed matrix (the LDS window's tail / the pad), which the helpers may read but whose values must not matter */
+#ifdef SRBM_M_GLOBAL
+#define DBG_WORKSPACE(tmp, Mw, np, count) HIPCHK((tmp).alloc(&(Mw), ((np) + DBG_PAD) * (count) * sizeof(double)))
+#else
+#define DBG_WORKSPACE(tmp, Mw, np, count) do { } while (0)
 #endif
+int srbm_debug_solve_mapped(int n, int nc, const int* map, int count, const double* M_packed, const double* rhs, double* x, int* nreg, double fill) {
     if (n <= 0 || n > SRBM_NUMAX || nc <= 0 || nc > n || count <= 0 || !map || !M_packed || !rhs || !x || !nreg) return fail("bad arguments");
     for (int k = 0; k < nc; k++) if (map[k] < 0 || map[k] >= n || (k > 0 && map[k] <= map[k - 1])) return fail("srbm_debug_solve_mapped: the map must be increasing and within [0, n)");
     const size_t np = (size_t)n * (n + 1) / 2, bytes = np * count * sizeof(double), vb = (size_t)n * count * sizeof(double);
-    double *dM = nullptr, *dr = nullptr, *dx = nullptr; int *dmap = nullptr, *dn = nullptr;
+    double *dM = nullptr, *dr = nullptr, *dx = nullptr, *Mw = nullptr; int *dmap = nullptr, *dn = nullptr;
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dr, vb)); HIPCHK(tmp.alloc(&dx, vb)); HIPCHK(tmp.alloc(&dmap, sizeof(int) * nc)); HIPCHK(tmp.alloc(&dn, sizeof(int) * count));
+    DBG_WORKSPACE(tmp, Mw, np, count);
     return run_dense_hook(srbm_k_debug_solve_mapped, count, DbgLds::END * sizeof(double), {{dM, M_packed, bytes}, {dr, rhs, vb}, {dmap, map, sizeof(int) * nc}},
-                          {{x, dx, vb}, {nreg, dn, sizeof(int) * count}}, n, nc, dmap, dM, dr, dx, dn);
+                          {{x, dx, vb}, {nreg, dn, sizeof(int) * count}}, n, nc, dmap, dM, dr, dx, dn, Mw, fill);
 }
 /* unit-test hook: x = M^-1 rhs through Cholesky + explicit inverse of the factor; X_packed = L^-1; ticks[2*count] */
-int srbm_debug_solve(int n, int count, const double* M_packed, const double* rhs, double* x, double* X_packed, int* ticks) {
-#ifdef SRBM_LARGE
-    return fail("srbm_debug_solve: the unit-test hooks of the dense blocks exist in the standard build only");
-#endif
+int srbm_debug_solve(int n, int count, const double* M_packed, const double* rhs, double* x, double* X_packed, int* ticks, double fill) {
     if (n <= 0 || n > SRBM_NUMAX || count <= 0 || !M_packed || !rhs || !x || !X_packed || !ticks) return fail("bad arguments");
     const size_t np = (size_t)n * (n + 1) / 2, bytes = np * count * sizeof(double), vb = (size_t)n * count * sizeof(double);
-    double *dM = nullptr, *dX = nullptr, *dr = nullptr, *dx = nullptr; int* dt = nullptr;
+    double *dM = nullptr, *dX = nullptr, *dr = nullptr, *dx = nullptr, *Mw = nullptr; int* dt = nullptr;
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dX, bytes)); HIPCHK(tmp.alloc(&dr, vb)); HIPCHK(tmp.alloc(&dx, vb));
     HIPCHK(tmp.alloc(&dt, sizeof(int) * 2 * count));
+    DBG_WORKSPACE(tmp, Mw, np, count);
     return run_dense_hook(srbm_k_debug_solve, count, DbgLds::XC * sizeof(double), {{dM, M_packed, bytes}, {dr, rhs, vb}},
-                          {{x, dx, vb}, {X_packed, dX, bytes}, {ticks, dt, sizeof(int) * 2 * count}}, n, dM, dr, dx, dX, dt);
+                          {{x, dx, vb}, {X_packed, dX, bytes}, {ticks, dt, sizeof(int) * 2 * count}}, n, dM, dr, dx, dX, dt, Mw, fill);
 }
-int srbm_debug_cholesky(int n, int count, const double* M_packed, double* L_packed, int* nreg) {
-#ifdef SRBM_LARGE
-    return fail("srbm_debug_cholesky: the unit-test hooks of the dense blocks exist in the standard build only");
-#endif
+int srbm_debug_cholesky(int n, int count, const double* M_packed, double* L_packed, int* nreg, double fill) {
     if (n <= 0 || n > SRBM_NUMAX || count <= 0 || !M_packed || !L_packed || !nreg) return fail("bad arguments");
     const size_t np = (size_t)n * (n + 1) / 2, bytes = np * count * sizeof(double);
-    double *dM = nullptr, *dL = nullptr; int* dr = nullptr;
+    double *dM = nullptr, *dL = nullptr, *Mw = nullptr; int* dr = nullptr;
     DevTemps tmp;
     HIPCHK(tmp.alloc(&dM, bytes)); HIPCHK(tmp.alloc(&dL, bytes)); HIPCHK(tmp.alloc(&dr, sizeof(int) * count));
+    DBG_WORKSPACE(tmp, Mw, np, count);
     return run_dense_hook(srbm_k_debug_cholesky, count, DbgLds::X * sizeof(double), {{dM, M_packed, bytes}}, {{L_packed, dL, bytes}, {nreg, dr, sizeof(int) * count}},
-                          n, dM, dL, dr);
+                          n, dM, dL, dr, Mw, fill);
+}
+/* unit-test hooks of the two mat-vecs of the IPM: y = H x for `count` packed symmetric n x n matrices H (lower triangle, row-major), through
+   dn_sym_matvec with H where the IPM keeps its normal matrix, and through hmatvec_packed with H in global memory as SrbmWork::H */
+int srbm_debug_sym_matvec(int n, int count, const double* H_packed, const double* xin, double* y) {
+    if (n <= 0 || n > SRBM_NUMAX || count <= 0 || !H_packed || !xin || !y) return fail("bad arguments");
+    const size_t np = (size_t)n * (n + 1) / 2, bytes = np * count * sizeof(double), vb = (size_t)n * count * sizeof(double);
+    double *dH = nullptr, *dx = nullptr, *dy = nullptr, *Mw = nullptr;
+    DevTemps tmp;
+    HIPCHK(tmp.alloc(&dH, bytes)); HIPCHK(tmp.alloc(&dx, vb)); HIPCHK(tmp.alloc(&dy, vb));
+#ifdef SRBM_M_GLOBAL
+    HIPCHK(tmp.alloc(&Mw, bytes));
+#endif
+    return run_dense_hook(srbm_k_debug_sym_matvec, count, DBG_SYM_MATVEC_LDS_BYTES, {{dH, H_packed, bytes}, {dx, xin, vb}}, {{y, dy, vb}}, n, dH, dx, dy, Mw);
+}
+int srbm_debug_hmatvec(int n, int count, const double* H_packed, const double* xin, double* y) {
+    if (n <= 0 || n > SRBM_NUMAX || count <= 0 || !H_packed || !xin || !y) return fail("bad arguments");
+    const size_t np = (size_t)n * (n + 1) / 2, bytes = np * count * sizeof(double), vb = (size_t)n * count * sizeof(double);
+    double *dH = nullptr, *dx = nullptr, *dy = nullptr;
+    DevTemps tmp;
+    HIPCHK(tmp.alloc(&dH, bytes)); HIPCHK(tmp.alloc(&dx, vb)); HIPCHK(tmp.alloc(&dy, vb));
+    return run_dense_hook(srbm_k_debug_hmatvec, count, DBG_HMATVEC_LDS_BYTES, {{dH, H_packed, bytes}, {dx, xin, vb}}, {{y, dy, vb}}, n, dH, dx, dy);
+}
+/* host only: where the IPM of this library puts the 2 (N - 3) compact dense state rows of width wc at n_u = nu (k3_sig_placement, the arithmetic of
+   its LDS map): out3 = rows in the tail of the packed-matrix window, rows behind the LDS map, 1 if all are in LDS (0: read from L2) */
+int srbm_debug_dense_row_placement(int N, int nu, int wc, int* out3) {
+    if (N < 4 || N > SRBM_NMAX || nu <= 0 || nu > SRBM_NUMAX || wc <= 0 || wc > K3_WCMAX || !out3) return fail("bad arguments");
+    const K3SigPlacement p = k3_sig_placement(N, nu, wc, (int)(K3_LDS_LAUNCH_BYTES / sizeof(double)));
+    out3[0] = p.in_tail; out3[1] = p.in_extra; out3[2] = p.sig_lds;
+    return 0;
 }
 // dbg and dbg2 of one instance, adjacent in SrbmWork: 384 doubles
 int srbm_debug_get_trace(srbm_batch* h, int inst, double* out384) {

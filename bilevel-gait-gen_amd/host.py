@@ -805,3 +805,13 @@ class BatchGaitOptimizer:
         st = np.zeros(n, np.int32); err = np.zeros(n, np.int32)
         self.mpc._chk(self.L.srbm_gait_get_candidate_status(self.g, _i(st), _i(err)))
         return st.reshape(-1, self.LS_SIZE), err.reshape(-1, self.LS_SIZE)
+
+
+def dense_row_placement(N, nu, wc, large=False):
+    """srbm_debug_dense_row_placement (host only, no GPU): where the IPM of that build puts the 2 (N - 3) compact dense state rows of width wc
+    at n_u = nu -- (rows in the tail of the packed-matrix window, rows behind the LDS map, True if all are in LDS; False: read from L2)"""
+    L = lib(large)
+    out = (C.c_int * 3)()
+    if L.srbm_debug_dense_row_placement(int(N), int(nu), int(wc), out) != 0:
+        raise ValueError(L.srbm_last_error().decode())
+    return out[0], out[1], bool(out[2])

@@ -276,6 +276,25 @@ class OracleMPC:
         return k, costs, q
 
 
+
+FEET0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)     # test/simulation_mpc.cpp:104-108
+
+
+def first_rti_sizes(cfg, phase=None):
+    """(n_u, wc, n_ineq) of the first RTI step from srb_init with the feet at FEET0: n_u = n - 12 (N + 1) spline variables, wc = n_force / 3 (the
+    width of the compact dense rows, srbm_k3_ipm.hiph), the inequality rows.  phase: after the cold start the contact times are set that far
+    apart, as many per foot as the cold start has"""
+    N = cfg['num_nodes']
+    s0 = np.array(cfg['srb_init'], float)
+    o = OracleMPC(cfg)
+    o.set_warmstart(s0)
+    o.initial_run(s0, FEET0)
+    if phase is not None:
+        o.set_contact_times([phase * np.arange(len(o.contact_times(e)[0])) for e in range(4)])
+    o.rti(s0, 0.0, FEET0)
+    sz = o.sizes()
+    return sz['n'] - 12 * (N + 1), sz['n_force'] // 3, sz['n_ineq']
+
 def qp_solve(P, q, A, b, cones, tol_gap=1e-8, tol_feas=1e-8):
     """cones: list of (is_nonneg, dim).  P dense symmetric, A dense."""
     L = lib()

@@ -62,8 +62,9 @@ def assert_bitwise(a, b, where):
             raise AssertionError('%s: %s differs at %s %s' % (where, k, 'instances' if a[k].ndim > 1 else 'entries', np.nonzero(diff)[0][:8].tolist()))
 
 
-def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False):
-    """cold start, then the one-step chain and the split launches from clones of the same state; returns the chain's counter deltas"""
+def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False, prepare=None):
+    """cold start, then the one-step chain and the split launches from clones of the same state; returns the chain's counter deltas.
+    prepare(batch): called after the cold start (e.g. a contact schedule of its own)"""
     states, ees = zip(*[make_inst(cfg, b) for b in range(B)])
     states, ees = np.array(states), np.array(ees).reshape(B, 12)
     base = host.BatchMPC(cfg, B, large=large)
@@ -71,6 +72,8 @@ def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False):
     base.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)          # the bench's settings
     base.set_solver_step_rule(*mode)
     base.create_initial_run(states, ees)
+    if prepare is not None:
+        prepare(base)
     if closed:                                                     # the pushes of tests/test_gpu_queue.py
         base.plant_set_state(states)
         imp = np.zeros((B, 6)); imp[::7, 0] = 0.4; imp[::11, 1] = -0.3
@@ -109,7 +112,7 @@ def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False):
     print('launch equivalence B=%d steps=%d mode=%s closed=%d: n_cu %d, multi-step launch kernel %s, queued launches %d, chain counters %s'
           % (B, steps, mode, closed, n_cu, info['kernel'], queued_launches, d))
     assert d['solves'] == B * steps
-    return dict(counters=d, n_cu=n_cu, queued_launches=queued_launches, kernel=info['kernel'])
+    return dict(counters=d, n_cu=n_cu, queued_launches=queued_launches, kernel=info['kernel'], sizes=[r['sizes'] for r in ref], err=[r['err'] for r in ref])
 
 
 def assert_attempts_and_back_off(d):

@@ -50,13 +50,15 @@ def make_batch(cfg, states, ees, step_rule=True, large=None):
 
 
 def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=True, min_alive=None, fused=False, large=None, x_tol=REL_TOL, start_mu=None,
-                    qp_extra=()):
+                    qp_extra=(), contact_phase=None):
     """cold start on both sides, then `steps` open-loop RTI steps (test/gait_opt_playground.cpp:113-126) with the device
     re-synchronised to the oracle before every step; returns per-step statistics.  Asserts entry-wise parity.
     fused=False: the device steps through srbm_get_real_time_update (host-pointer entry, one launch per phase: the lower-start attempt is
     never made there).  fused=True: through srbm_rti_advance(i, 1) -- the device-resident launch bench.py times, which takes node 1 and the
     spline feet of the installed trajectory as its inputs and, with start_mu > 0, begins every solve with the lower-start ATTEMPT.
-    The assembled QP and the duals are compared at the steps i % qp_every == 0 and at the steps in qp_extra; primal and states at every step."""
+    The assembled QP and the duals are compared at the steps i % qp_every == 0 and at the steps in qp_extra; primal and states at every step.
+    contact_phase: after the cold start the oracles' contact times are set that far apart (as many per foot as they have); the device takes the
+    schedule over with the first installed trajectory."""
     B = len(states)
     N = cfg['num_nodes']
     dt = cfg['integrator_dt']
@@ -74,9 +76,14 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
     for b in range(B):
         so = oracles[b].stats()['status']
         assert cls(st0[b]) == cls(so) or {cls(st0[b]), cls(so)} <= {'solved', 'maxiter'}, (b, st0[b], so)
+    if contact_phase is not None:
+        for o in oracles:
+            o.set_contact_times([contact_phase * np.arange(len(o.contact_times(e)[0])) for e in range(4)])
     seen_sizes, seen_td, worst = set(), 0, dict(A=0.0, x=0.0, x_inacc=0.0, z=0.0, z_all=0.0, Atz=0.0, states=0.0, x_cert_oracle=0.0, x_cert_gpu=0.0, x_cert_gpu_where_oracle_gave_up=0.0,
                                                dual_obj=0.0, kkt=0.0)
     n_cert = 0
+    n_xcmp = 0
+    seen_shapes = set()          # (n, n_force) of the compared solves
     n_inacc = 0
     n_atz = 0
     n_gave_up = n_gave_up_cert = 0
@@ -147,7 +154,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
             # Solved / SolvedInacc / MaxIter steer the RTI step identically (msrb.cpp:136-144); which of them an IPM reports at a
             # 1e-15 gap tolerance is solver-internal (Clarabel is unpinned).  Infeasible must match exactly.
             assert co == cg or {co, cg} <= {'solved', 'maxiter'}, (i, b, sos[b], st[b])
-            out = dict(exact=int(int(sos[b]) == int(st[b])), n=n, ntd=osz['n_td'])
+            out = dict(exact=int(int(sos[b]) == int(st[b])), n=n, nf=osz['n_force'], ntd=osz['n_td'])
             # knot tables after the step (horizon shift of this step included): bit-exact
             ta = traj_after[b]
             for ee in range(4):
@@ -173,6 +180,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
                 return out              # an unconverged QP: the iterate it stopped at is solver-specific
             xo = o.x()
             out['x'] = max(relerr(xr[b, :n], o.qp_x()), relerr(x[b, :n], xo))
+            out['x_compared'] = 1
             if int(st[b]) == 1:
                 # the DEVICE itself reports SolvedInacc where the oracle reports Solved: counted, located, and held to the SAME bound as every other
                 # pair (round 4 allowed 10 x here)
@@ -251,7 +259,8 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
                 continue
             total += 1
             exact_status += r['exact']
-            seen_sizes.add(r['n']); seen_td += r['ntd'] > 0
+            seen_sizes.add(r['n']); seen_shapes.add((r['n'], r['nf'])); seen_td += r['ntd'] > 0
+            n_xcmp += r.get('x_compared', 0)
             n_unique += r.get('z_unique', 0)
             n_cert += r.get('cert', 0)
             n_inacc += r.get('inacc', 0)
@@ -272,7 +281,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
         assert ctr['low_tried'] >= 0.8 * ctr['solves'], ctr
     # (a device SolvedInacc where the oracle says Solved is a CLASSIFICATION difference of two interior-point codes at the fp64 floor -- observed on 13 of
     #  5 102 host-driven solves, all within 6e-11 of the oracle's minimiser; every such pair is held to the full bound above and listed in the result)
-    return dict(inacc=n_inacc, inacc_where=inacc_where, duals_compared_on_row_space=n_atz, oracle_gave_up=n_gave_up, device_certified_where_oracle_gave_up=n_gave_up_cert, x_by_step=x_by_step, counters=ctr, alive=int(alive.sum()), sizes=seen_sizes, td_steps=seen_td, worst=worst, exact_status=exact_status, total=total, z_unique=n_unique, certified=n_cert)
+    return dict(inacc=n_inacc, inacc_where=inacc_where, duals_compared_on_row_space=n_atz, oracle_gave_up=n_gave_up, device_certified_where_oracle_gave_up=n_gave_up_cert, x_by_step=x_by_step, counters=ctr, alive=int(alive.sum()), sizes=seen_sizes, shapes=seen_shapes, x_compared=n_xcmp, td_steps=seen_td, worst=worst, exact_status=exact_status, total=total, z_unique=n_unique, certified=n_cert)
 
 
 def test_config_b_all_256_instances_entrywise_over_20_steps():
