@@ -230,14 +230,26 @@ extern "C" {
 
 const char* srbm_last_error(void) { return g_err.c_str(); }
 long srbm_bytes_per_instance(void) { return (long)(sizeof(SrbmInst) + sizeof(SrbmWork)); }
-/* diagnostic builds (-DSRBM_PROFILE) only: cycles per IPM phase of one instance, 16 slots */
-int srbm_debug_get_profile(srbm_batch* h, int inst, double* out16) {
-    if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    return fetch(h, {{out16, work_field(h, inst, offsetof(SrbmWork, prof)), sizeof(double) * 16}});
+/* diagnostic builds (-DSRBM_PROFILE) only: the cycle record of one instance, srbm_debug_profile_slot(-1, ..) slots (srbm_prof.hiph) */
+int srbm_debug_get_profile(srbm_batch* h, int inst, double* out) {
+    if (!h || inst < 0 || inst >= h->batch || !out) return fail("bad arguments");
+    return fetch(h, {{out, work_field(h, inst, offsetof(SrbmWork, prof)), sizeof(double) * SRBM_PROF_NSLOTS}});
 }
-int srbm_debug_get_profile2(srbm_batch* h, int inst, double* out96) {
-    if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    return fetch(h, {{out96, work_field(h, inst, offsetof(SrbmWork, prof2)), sizeof(double) * 96}});
+/* the number of cycle slots; for 0 <= k below it, the printable name of slot k and of its group (the lists of srbm_prof.hiph) */
+int srbm_debug_profile_slot(int k, const char** name, const char** group) {
+#define SRBM_PROF_X_NAME(id, text) text,
+#define SRBM_PROF_X_SLOT_NAME(grp, id, text) {text, SRBM_PROF_G_##grp},
+    static const char* const groups[SRBM_PROF_NGROUPS] = { SRBM_PROF_GROUPS(SRBM_PROF_X_NAME) };
+    static const struct { const char* name; int group; } slots[SRBM_PROF_NSLOTS] = { SRBM_PROF_SLOTS(SRBM_PROF_X_SLOT_NAME) };
+    if (k >= 0 && k < SRBM_PROF_NSLOTS && name && group) { *name = slots[k].name; *group = groups[slots[k].group]; }
+    return SRBM_PROF_NSLOTS;
+}
+/* the number of fields of a traced iteration, and in *iters the iterations srbm_debug_get_trace returns; for 0 <= k below it, the printable name of field k */
+int srbm_debug_trace_field(int k, const char** name, int* iters) {
+    static const char* const fields[SRBM_TRACE_NFIELDS] = { SRBM_TRACE_FIELDS(SRBM_PROF_X_NAME) };
+    if (k >= 0 && k < SRBM_TRACE_NFIELDS && name) *name = fields[k];
+    if (iters) *iters = SRBM_TRACE_ITERS;
+    return SRBM_TRACE_NFIELDS;
 }
 /* unit-test hooks of the dense blocks (srbm_dense_hooks.hiph), in both builds: the packed matrices where the IPM keeps its normal matrix -- the
    LDS (standard build) or, SRBM_M_GLOBAL, a device workspace of one slice per matrix with DBG_PAD doubles after each --; `fill` is written to
@@ -309,10 +321,10 @@ int srbm_debug_dense_row_placement(int N, int nu, int wc, int* out3) {
     out3[0] = p.in_tail; out3[1] = p.in_extra; out3[2] = p.sig_lds;
     return 0;
 }
-// dbg and dbg2 of one instance, adjacent in SrbmWork: 384 doubles
-int srbm_debug_get_trace(srbm_batch* h, int inst, double* out384) {
-    if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
-    return fetch(h, {{out384, work_field(h, inst, offsetof(SrbmWork, dbg)), sizeof(double) * 384}});
+// the trace of one instance, row by row: (iterations) x (fields) doubles, both numbers from srbm_debug_trace_field
+int srbm_debug_get_trace(srbm_batch* h, int inst, double* out) {
+    if (!h || inst < 0 || inst >= h->batch || !out) return fail("bad arguments");
+    return fetch(h, {{out, work_field(h, inst, offsetof(SrbmWork, trace)), sizeof(SrbmWork::trace)}});
 }
 
 // diagnostic: the spline variables of the linearisation point and of the QP minimiser of instance `inst`, with the column descriptors

@@ -119,6 +119,9 @@ typedef struct SrbmSample {   /* one force sample time (10 per stance phase): ro
     int idx, cnt, ee, pad;
 } SrbmSample;
 
+#define SRBM_PROF_CAP 112          /* cycle slots of the diagnostic record (srbm_prof.hiph names SRBM_PROF_NSLOTS of them) */
+#define SRBM_TRACE_ITERS 32        /* IPM iterations the diagnostic trace keeps */
+#define SRBM_TRACE_FIELD_CAP 12    /* fields per traced iteration */
 typedef struct SrbmWork {
     /* ---- assembly (kernel 1) ---- */
     SrbmNodeRec node[SRBM_NMAX + 1][SRBM_NEE];
@@ -161,10 +164,8 @@ typedef struct SrbmWork {
     double Ms[SRBM_HPACK];                        /* gait step: H + G' diag(lambda/s) G of the last solution (srbm_k3_normal_matrix) */
     double w0[SRBM_MIMAX];                        /* IPM: unit weight of the row/cost-scaled problem, e_r^2 / c (kernel 3 scratch) */
     double hrow_g[SRBM_MIMAX];                    /* IPM: right-hand sides of the inequality rows (large build: read from here instead of held in registers) */
-    double prof2[96];                             /* diagnostic builds only: fine-grained stamps (K3_FINE) */
-    double prof[16];                              /* diagnostic builds only (-DSRBM_PROFILE): cycles per IPM phase */
-    double dbg[4 * 64];
-    double dbg2[4 * 32];                          /* diagnostic builds only: worst refinement row (index, s, lambda, e2) */                           /* diagnostic builds only: per-iteration (mu, alpha_aff, alpha, gap_rel) */
+    double prof[SRBM_PROF_CAP];                   /* diagnostic builds only (-DSRBM_PROFILE, srbm_prof.hiph): cycles per named slot, accumulated over every launch on the batch */
+    double trace[SRBM_TRACE_ITERS * SRBM_TRACE_FIELD_CAP];   /* diagnostic builds only: per IPM iteration of the last solve, one row of named fields */
 } SrbmWork;
 
 /* launch arguments of the fused RTI kernel (srbm_fused.hiph) besides the batch: the closed-loop mode (plant != nullptr, srbm_plant.hiph) and the two

@@ -1,4 +1,4 @@
-"""Diagnostic: per-phase cycle shares of the IPM kernel (build with -DSRBM_PROFILE; never quote its run time)."""
+"""Diagnostic: per-phase cycle shares of the IPM kernel (build with -DSRBM_PROFILE; never quote its run time); the coarse table: sums over the slot groups."""
 import importlib.util, os, sys, ctypes as C
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,28 +16,29 @@ if mode == 'lower_start':
 elif mode == 'step_rule':
     gb.enable_fast_termination()
 print('solver settings', gb.solver_step_rule())
-gb.create_initial_run(s0, ee)
-gb.rti_advance(0, 4); gb.synchronize()
-out = np.zeros(16)
-gb.L.srbm_debug_get_profile(gb.h, 0, out.ctypes.data_as(C.POINTER(C.c_double)))
-names = ['misc/loop', 'H->LDS', 'row residuals', "G'lam", 'Hu+term', 'M sparse', 'M dense SYR2K', 'Cholesky', 'aff first solve', 'aff refine', 'corr first solve', 'corr refine', 'step update']
-tot = out.sum()
-print('iters', gb.stats()[0, 4], 'total stamp ticks %.0f' % tot)
-for n, v in zip(names, out):
-    print('%-18s %10.0f  %5.1f%%' % (n, v, 100 * v / tot))
 
-out2 = np.zeros(96)
-gb.L.srbm_debug_get_profile2(gb.h, 0, out2.ctypes.data_as(C.POINTER(C.c_double)))
-names2 = {11: 'H u (two triangular mat-vecs, LDS)', 12: 'dual residual loop + reductions + termination', 0: 'other->eval', 1: 'eval: force samples', 2: 'eval: dense rows', 3: 'other->gt', 4: 'gt: cs', 5: 'gt: dense rows', 6: 'gt: reduce + epilogue', 50: '  gt: dense rows (LDS)', 51: '  gt: sparse / position part', 7: 'other->M', 8: 'M force blocks', 52: '  M (c) dense rows: compact MFMA blocks', 53: '  M (d) dense rows x position coefficients', 9: 'M (b) position blocks', 10: 'M dense + factor + invert', 20: '  tiles <- LDS', 21: '  cholesky', 22: '  invert diag blocks', 23: '  trtri', 24: '  rank-2 update (MFMA)',
-          30: 'dir: (other)', 31: 'dir: row rhs', 33: 'dir: col rhs (after G\' pass)', 34: 'dir: tri solves', 35: 'dir: row products (after G pass)',
-          36: 'ref: e2 + row write', 32: 'ref: (G\' pass, in 4-6)', 37: 'ref: H du (L2)', 38: 'ref: e1 + err reductions', 39: 'ref: corr rhs (after G\' pass)', 40: 'ref: tri solves', 41: 'ref: row products + update', 42: 'ref: exit',
-          43: 'ds + step length', 44: 'gz: targets + row write', 45: 'gz: col rhs (after G\' pass)', 46: 'gz: tri solves', 47: 'gz: row products + step'}
-print('phases between two solves in the fused launch, ticks per RTI step (4 steps): update %.0f, next inputs %.0f, assemble %.0f, condense %.0f; IPM solve of the last step %.0f' % (out2[56] / 4, out2[57] / 4, out2[58] / 4, out2[59] / 4, tot))
-print('fine stamps (accumulated over all RTI steps of this process; shares of their sum):')
-k1n = ['staging of the knot tables', 'horizon shift', 'variable bookkeeping', 'linearisation point + column map', 'node records + force samples', 'equality rows', 'node blocks + affine term']
-k4n = ['staging, F/R values, B u', 'rollout', 'costates', 'assemble + position-row duals', 'candidates', 'spline-variable cost', 'directional derivative + Armijo', 'x update + states', 'spline node values']
-print('kernel-1 phases (ticks, all steps of this process): ' + '; '.join('%s %.0f' % (n, v) for n, v in zip(k1n, out2[64:71])))
-print('kernel-4 phases (ticks, all steps of this process): ' + '; '.join('%s %.0f' % (n, v) for n, v in zip(k4n, out2[72:81])))
-out2[7] = 0; out2[56:] = 0; tot2 = out2.sum()
-for k, n in names2.items():
-    print('%-28s %12.0f %5.1f%%' % (n, out2[k], 100 * out2[k] / tot2))
+name, group = C.c_char_p(), C.c_char_p()
+slots = []                                               # (name, group) of every cycle slot, as the library names them
+for k in range(gb.L.srbm_debug_profile_slot(-1, None, None)):
+    gb.L.srbm_debug_profile_slot(k, C.byref(name), C.byref(group)); slots.append((name.value.decode(), group.value.decode()))
+groups = list(dict.fromkeys(g for _, g in slots))
+def record():
+    gb.synchronize(); out = np.zeros(len(slots)); gb.L.srbm_debug_get_profile(gb.h, 0, out.ctypes.data_as(C.POINTER(C.c_double)))
+    return out
+gb.create_initial_run(s0, ee)
+gb.rti_advance(0, 3)
+before = record()
+gb.rti_advance(3, 1)
+last = record() - before                                 # the fourth RTI step alone
+in_group = lambda g: [(n, v) for v, (n, gs) in zip(last, slots) if gs == g]
+total = lambda g: sum(v for _, v in in_group(g))
+ipm = [g for g in groups if g.startswith('ipm: ')]
+tot = sum(total(g) for g in ipm)
+print('iters', gb.stats()[0, 4], 'total stamp ticks %.0f' % tot)
+for g in ipm:
+    print('%-18s %10.0f  %5.1f%%' % (g[5:], total(g), 100 * total(g) / tot))
+print('fine stamps (all of the last RTI step, as the table above; shares of its IPM solve):')
+for g in groups:
+    if g.startswith('step: '): print('%s, ticks: %.0f (%s)' % (g[6:], total(g), '; '.join('%s %.0f' % nv for nv in in_group(g))))
+for g in ipm:
+    for n, v in in_group(g): print('%-58s %12.0f %5.1f%%' % (n, v, 100 * v / tot))

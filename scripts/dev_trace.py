@@ -16,7 +16,9 @@ for i in range(nsteps):
     g.rti_advance(i, 1)
 g.synchronize()
 print('counters', g.solver_counters()); print('status', g.status(), 'stats', g.stats()[0], 'sizes', g.sizes()[0])
-out = np.zeros(384)
-g.L.srbm_debug_get_trace(g.h, 0, out.ctypes.data_as(C.POINTER(C.c_double)))
-for it in range(int(g.stats()[0, 4]) + 1):
-    if it < 32: print(it, 'mu %.3e sigma %.3e alpha %.3e gap %.3e res_p %.2e res_d %.2e ir %d err %.2e' % tuple(out[8 * it:8 * it + 8]), 'alpha_aff %.3f |du_aff|/|u| %.2e  worst refinement row %d e2 %.2e' % tuple(out[256 + 4 * it:256 + 4 * it + 4]))
+name, traced, fields = C.c_char_p(), C.c_int(), []
+for k in range(g.L.srbm_debug_trace_field(-1, None, None)): g.L.srbm_debug_trace_field(k, C.byref(name), C.byref(traced)); fields.append(name.value.decode())
+rows = np.zeros((traced.value, len(fields)))         # one row per traced iteration
+g.L.srbm_debug_get_trace(g.h, 0, rows.ctypes.data_as(C.POINTER(C.c_double)))
+for it in range(min(int(g.stats()[0, 4]) + 1, len(rows))):
+    print(it, ' '.join('%s %.4g' % nv for nv in zip(fields, rows[it])))

@@ -181,8 +181,8 @@ if os.path.exists(os.path.join(src, 'phase_shares_reference_criterion.txt')):
     shutil.copy(os.path.join(src, 'phase_shares_reference_criterion.txt'), os.path.join(dst, 'ipm_phase_shares_reference_criterion.txt'))
 if os.path.exists(os.path.join(src, 'phase_shares.txt')):
     shutil.copy(os.path.join(src, 'phase_shares.txt'), os.path.join(dst, 'ipm_phase_shares.txt'))
-    # the two numbers rounds are compared by: cycles of one IPM iteration and the share of the dense phase, from the coarse stamps
-    # of the diagnostic build (scripts/dev_prof.py: last solve of instance 0 after 4 RTI steps)
+    # the two numbers rounds are compared by: cycles of one IPM iteration and the share of the dense phase, from the coarse table
+    # of the diagnostic build (scripts/dev_prof.py: fourth RTI step of instance 0, sums over the slot groups)
     try:
         txt = open(os.path.join(src, 'phase_shares.txt')).read().splitlines()
         it_line = [l for l in txt if l.startswith('iters ')][0].split()
