@@ -79,6 +79,8 @@ struct srbm_batch {
     size_t scratch_bytes = 0;
     void* h_stage = nullptr;         // pinned host mirror of d_scratch for the per-tick entries: ONE copy in, ONE copy out per call
     size_t stage_bytes = 0;
+    double* d_log = nullptr;         // step log [log_cap][batch][SRBM_STEP_LOG_DOUBLES] (srbm_steplog.hiph), nullptr: logging off
+    int log_cap = 0, log_used = 0;   // slots allocated; the cursor: slots written by the launches queued so far
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -188,6 +190,22 @@ static int use_batch(srbm_batch* h) {
 }
 // the IPM variant of every launch path: the _long kernels beyond K3_SHORT_N nodes (srbm_k3_ipm.hiph)
 static bool k3_long(const srbm_batch* h) { return h->hp.N > K3_SHORT_N; }
+// ---- step log (srbm_steplog.hiph): the entries that log ask for room BEFORE they queue anything, so that a refused call leaves the batch untouched ----
+static int log_room(const srbm_batch* h, const char* fn, int steps) {
+    if (!h->d_log || steps <= h->log_cap - h->log_used) return 0;
+    return fail(std::string(fn) + ": the step log has room for " + std::to_string(h->log_cap - h->log_used) + " more steps (" + std::to_string(h->log_used) +
+                " of " + std::to_string(h->log_cap) + " logged), the call asks for " + std::to_string(steps) +
+                " (srbm_step_log_reset, or srbm_step_log_enable with more steps)");
+}
+static SrbmStepLogArgs log_args(const srbm_batch* h) { return SrbmStepLogArgs{h->d_log, h->log_used, h->batch}; }
+// the record of the one-step launch just queued (launch_step): its own small kernel behind the four phase kernels
+static int log_one_step(srbm_batch* h) {
+    if (!h->d_log) return 0;
+    hipLaunchKernelGGL(srbm_k_step_log, dim3(h->batch), dim3(64), 0, h->stream, h->insts, h->d_state, h->d_time, h->d_ee, log_args(h));
+    HIPCHK(hipGetLastError());
+    h->log_used++;
+    return 0;
+}
 // One RTI step on inputs already in h->d_state / d_time / d_ee: four kernels.  exact: the solve is taken to the gap criterion whatever the batch's
 // step rule says (the solve whose KKT sensitivity the gait step differentiates).
 // (Measured in round 5: the same step as ONE launch of the fused kernel -- no grid-wide wait between the phases, a workgroup through with its line-search
@@ -347,7 +365,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->dp); (void)hipFree(h->insts); (void)hipFree(h->works); (void)hipFree(h->queues);
     (void)hipFree(h->d_state); (void)hipFree(h->d_time); (void)hipFree(h->d_ee);
     (void)hipFree(h->d_plant); (void)hipFree(h->d_push_time); (void)hipFree(h->d_push_impulse);
-    (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage);
+    (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage); (void)hipFree(h->d_log);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -374,6 +392,10 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
         {reinterpret_cast<const void*>(srbm_rti_fused_long), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_rti_queued), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_rti_queued_long), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_fused_logged), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_fused_long_logged), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_queued_logged), K3_LDS_LAUNCH_BYTES},
+        {reinterpret_cast<const void*>(srbm_rti_queued_long_logged), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_k3_normal_matrix), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_k_gait_sensitivity), KG_DYN_LDS_BYTES}};
     for (const auto& k : dyn_lds) HIPCHK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
@@ -616,21 +638,24 @@ int srbm_create_initial_run(srbm_batch* h, const double* state, const double* ee
 }
 int srbm_get_real_time_update(srbm_batch* h, const double* state, const double* init_time, const double* ee) {
     if (!h || !state || !init_time || !ee) return fail("bad arguments");
+    if (log_room(h, "srbm_get_real_time_update", 1)) return -1;
     HIPCHK(hipSetDevice(h->device));
     if (upload_inputs(h, state, init_time, ee)) return -1;
-    if (launch_step(h)) return -1;
+    if (launch_step(h) || log_one_step(h)) return -1;
     return srbm_synchronize(h);
 }
 int srbm_get_real_time_update_dev(srbm_batch* h, const double* state_dev, const double* time_dev, const double* ee_dev) {
     if (!h || !state_dev || !time_dev || !ee_dev) return fail("bad arguments");
+    if (log_room(h, "srbm_get_real_time_update_dev", 1)) return -1;
     HIPCHK(hipSetDevice(h->device));
     const size_t B = h->batch;
     HIPCHK(hipMemcpyAsync(h->d_state, state_dev, sizeof(double) * 13 * B, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_ee, ee_dev, sizeof(double) * 12 * B, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_time, time_dev, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream));
-    return launch_step(h);
+    return launch_step(h) || log_one_step(h) ? -1 : 0;
 }
-static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs pl) {
+static int launch_fused(srbm_batch* h, const char* fn, int first_index, int steps, SrbmPlantArgs pl) {
+    if (log_room(h, fn, steps)) return -1;
     // (the lower-start attempt rests on the linearisation point being close to the new minimiser: true for the open-loop protocol, whose state IS
     //  node 1 of the plan; under a plant -- integration error every step, pushes -- it is repeated too often to pay: closed loop 62 k it/s with, 80 k without)
     pl.tol_step = h->hp.tol_step; pl.start_mu = pl.plant ? 0.0 : h->hp.start_mu;
@@ -643,26 +668,38 @@ static int launch_fused(srbm_batch* h, int first_index, int steps, SrbmPlantArgs
     // a batch larger than the chip, several steps: a resident grid takes (instance, step) items from the step queues (srbm_fused.hiph)
     const bool queued = h->queued_ok && h->batch > h->n_cu && steps > 1 && steps <= SRBM_QUEUE_MAX_STEPS && h->batch <= SRBM_QUEUE_MAX_BATCH;
     const bool long_n = k3_long(h);
-    h->last_launch_kernel = (queued ? 3 : 1) + (long_n ? 1 : 0);          // the codes of srbm_debug_get_launch_info
+    h->last_launch_kernel = (queued ? 3 : 1) + (long_n ? 1 : 0);          // the codes of srbm_debug_get_launch_info (a logged launch: its unlogged twin's)
     h->last_launch_steps = steps;
+    const bool logged = h->d_log != nullptr;                              // the logged twin of the same kernel: step s to slot log_used + s
     if (queued) {
         if (!h->queues) HIPCHK(hipMalloc(&h->queues, sizeof(SrbmQueue) * SRBM_NQUEUES));
         hipLaunchKernelGGL(srbm_k_queue_init, dim3(SRBM_NQUEUES), dim3(256), 0, h->stream, h->queues, h->batch);
-        const auto kernel = long_n ? srbm_rti_queued_long : srbm_rti_queued;
-        hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                           h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
+        if (logged) {
+            const auto kernel = long_n ? srbm_rti_queued_long_logged : srbm_rti_queued_logged;
+            hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
+                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch, log_args(h));
+        } else {
+            const auto kernel = long_n ? srbm_rti_queued_long : srbm_rti_queued;
+            hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
+                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
+        }
+    } else if (logged) {
+        const auto kernel = long_n ? srbm_rti_fused_long_logged : srbm_rti_fused_logged;
+        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
+                           h->d_state, h->d_time, h->d_ee, pl, log_args(h));
     } else {
         const auto kernel = long_n ? srbm_rti_fused_long : srbm_rti_fused;
         hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
                            h->d_state, h->d_time, h->d_ee, pl);
     }
+    if (logged) h->log_used += steps;
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = steps; h->ev_used++; }
     HIPCHK(hipGetLastError());
     return 0;
 }
 int srbm_rti_advance(srbm_batch* h, int first_index, int steps) {
     if (!h || steps < 0) return fail("bad arguments");
-    return launch_fused(h, first_index, steps, SrbmPlantArgs{nullptr, nullptr, nullptr, 1, 0, 0.0, 0.0});
+    return launch_fused(h, "srbm_rti_advance", first_index, steps, SrbmPlantArgs{nullptr, nullptr, nullptr, 1, 0, 0.0, 0.0});
 }
 
 // ---- closed-loop rollout harness (srbm_plant.hiph) ----
@@ -701,19 +738,71 @@ int srbm_plant_set_push(srbm_batch* h, const double* time, const double* impulse
 int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int substeps, int advance_time) {
     if (!h || steps < 0 || substeps < 1) return fail("bad arguments");
     if (!h->d_plant) return fail("the plant state has not been set (srbm_plant_set_state)");
-    return launch_fused(h, first_index, steps, SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push_time : nullptr, h->push_set ? h->d_push_impulse : nullptr,
+    return launch_fused(h, "srbm_closed_loop_advance", first_index, steps, SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push_time : nullptr, h->push_set ? h->d_push_impulse : nullptr,
                                                               substeps, advance_time ? 1 : 0});
 }
 // the same protocol, one kernel launch per phase and step (grid-wide synchronisation between the phases); kept for
 // A/B measurements against the fused kernel
 int srbm_rti_advance_unfused(srbm_batch* h, int first_index, int steps) {
     if (!h || steps < 0) return fail("bad arguments");
+    if (log_room(h, "srbm_rti_advance_unfused", steps)) return -1;
     if (use_batch(h)) return -1;
     for (int i = 0; i < steps; i++) {
         const double time = (first_index + i) * h->hp.dt;
         hipLaunchKernelGGL(srbm_k_next_inputs, dim3(h->batch), dim3(64), 0, h->stream, h->dp, h->insts, time, h->d_state, h->d_time, h->d_ee);
-        if (launch_step(h)) return -1;
+        if (launch_step(h) || log_one_step(h)) return -1;
     }
+    return 0;
+}
+
+// ---- the step log (include/srbm_rti.h; csrc/srbm_steplog.hiph) ----
+int srbm_step_log_record_doubles(void) { return SRBM_STEP_LOG_DOUBLES; }
+int srbm_step_log_enable(srbm_batch* h, int max_steps) {
+    if (!h || max_steps < 0) return fail("srbm_step_log_enable: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_log) HIPCHK(hipFree(h->d_log));
+    h->d_log = nullptr; h->log_cap = 0; h->log_used = 0;
+    if (max_steps == 0) return 0;
+    const size_t bytes = sizeof(double) * SRBM_STEP_LOG_DOUBLES * (size_t)h->batch * (size_t)max_steps;
+    HIPCHK(hipMalloc(&h->d_log, bytes));
+    h->log_cap = max_steps;
+    return 0;
+}
+int srbm_step_log_reset(srbm_batch* h) {
+    if (!h) return fail("srbm_step_log_reset: bad arguments");
+    h->log_used = 0;
+    return 0;
+}
+int srbm_step_log_count(srbm_batch* h, int* steps_logged) {
+    if (!h || !steps_logged) return fail("srbm_step_log_count: bad arguments");
+    *steps_logged = h->log_used;
+    return 0;
+}
+// the device address of slots [first_slot, first_slot + count) once the range is known to be logged
+static int log_range(const srbm_batch* h, const char* fn, int first_slot, int count, const void* out, const double** src, size_t* bytes) {
+    if (!h || !out) return fail(std::string(fn) + ": bad arguments");
+    if (!h->d_log) return fail(std::string(fn) + ": no step log is enabled on this batch (srbm_step_log_enable)");
+    if (first_slot < 0 || count < 0 || first_slot > h->log_used || count > h->log_used - first_slot)
+        return fail(std::string(fn) + ": slots [" + std::to_string(first_slot) + ", " + std::to_string((long long)first_slot + count) + ") are outside the " +
+                    std::to_string(h->log_used) + " steps logged");
+    const size_t rec = (size_t)SRBM_STEP_LOG_DOUBLES * h->batch;
+    *src = h->d_log + rec * first_slot;
+    *bytes = sizeof(double) * rec * count;
+    return 0;
+}
+int srbm_step_log_get(srbm_batch* h, int first_slot, int count, double* out) {
+    const double* src = nullptr; size_t bytes = 0;
+    if (log_range(h, "srbm_step_log_get", first_slot, count, out, &src, &bytes)) return -1;
+    if (bytes == 0) return 0;
+    return fetch(h, {{out, src, bytes}});
+}
+int srbm_step_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev) {
+    const double* src = nullptr; size_t bytes = 0;
+    if (log_range(h, "srbm_step_log_copy_dev", first_slot, count, out_dev, &src, &bytes)) return -1;
+    if (bytes == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out_dev, src, bytes, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 int srbm_synchronize(srbm_batch* h) {

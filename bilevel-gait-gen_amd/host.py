@@ -154,6 +154,36 @@ SOLVE_TYPE_NAMES = {0: 'Solved', 1: 'Solved Inacc', 2: 'Max Iter', 3: 'P - Infea
                     6: 'D - Infeasible Inacc', 7: 'Unsolved'}      # MPC::PrintStatLineToFile, mpc.cpp:944-972
 
 
+# One record of the step log (include/srbm_rti.h: srbm_step_log_*): field name -> slice of its STEP_LOG_DOUBLES doubles; [58, 64) is reserved
+STEP_LOG_DOUBLES = 64
+STEP_LOG_FIELDS = {
+    'solve_number': slice(0, 1), 'init_time': slice(1, 2), 'status': slice(2, 3), 'err': slice(3, 4), 'solve_flags': slice(4, 5),
+    'n': slice(5, 6), 'm': slice(6, 7), 'stats': slice(7, 15), 'qp_cost': slice(15, 16), 'merit_dd': slice(16, 17),
+    'state': slice(17, 30), 'ee': slice(30, 42), 'force': slice(42, 54), 'in_contact': slice(54, 58)}
+MERIT_MU = 5000.0        # MPC::GetMeritValue (mpc.cpp:749-753); the library's srbm_get_merit uses the same constant
+
+
+def format_stat_line(solve_number, time_ms, stats, merit, merit_dd, status):
+    """one table row of MPC::PrintStatLineToFile (mpc.cpp:974-989) from the values of one solve; stats as srbm_get_stats"""
+    cw = 15
+    s = stats
+    vals = ['%d' % solve_number, '%g' % time_ms, '%g' % s[2], '%g' % s[3], '%g' % s[0], '%g' % s[1], '%g' % merit, '%g' % merit_dd,
+            SOLVE_TYPE_NAMES.get(int(status), 'Other'), '%g' % s[1]]       # last column: cost_ = GetCostValue(prev_qp_sol), the same value as 'Cost' (mpc.cpp:809, msrb.cpp:183-184)
+    return ''.join(v.ljust(cw) for v in vals) + '\n'
+
+
+def step_log_merit(record):
+    """the 'Merit' column of a step-log record (or an array of them): cost + mu * defect, formed as srbm_get_merit forms it"""
+    record = np.asarray(record)
+    return record[..., 8] + MERIT_MU * record[..., 9]
+
+
+def stat_line_from_log(fh, record, time_ms):
+    """the row print_stat_line writes after a one-step launch, from one step-log record [STEP_LOG_DOUBLES] of that solve"""
+    r = np.asarray(record, dtype=np.float64)
+    fh.write(format_stat_line(int(r[0]), time_ms, r[STEP_LOG_FIELDS['stats']], step_log_merit(r), r[16], r[2]))
+
+
 def _d(a):
     return a.ctypes.data_as(_dp)
 
@@ -488,6 +518,31 @@ class BatchMPC:
     def closed_loop_advance(self, first_index, steps, substeps=1, advance_time=False):
         self._chk(self.L.srbm_closed_loop_advance(self.h, int(first_index), int(steps), int(substeps), int(bool(advance_time))))
 
+    # ---- the step log: every step of a multi-step launch (include/srbm_rti.h: srbm_step_log_*) ----
+    def step_log_enable(self, max_steps):
+        """room for max_steps steps of this batch, cursor 0; 0 disables logging and frees the buffer.  A clone has logging off"""
+        self._chk(self.L.srbm_step_log_enable(self.h, int(max_steps)))
+
+    def step_log_reset(self):
+        self._chk(self.L.srbm_step_log_reset(self.h))
+
+    def step_log_count(self):
+        n = C.c_int(0)
+        self._chk(self.L.srbm_step_log_count(self.h, C.byref(n)))
+        return n.value
+
+    def step_log(self, first=0, count=None):
+        """the records of slots [first, first + count) as an array [count][batch][STEP_LOG_DOUBLES] (STEP_LOG_FIELDS names the columns); synchronous"""
+        count = self.step_log_count() - first if count is None else count
+        a = np.zeros((max(int(count), 0), self.batch, STEP_LOG_DOUBLES))
+        self._chk(self.L.srbm_step_log_get(self.h, int(first), int(count), _d(a)))
+        return a
+
+    def step_log_copy_dev(self, ptr, first=0, count=None):
+        """the same records to device memory at `ptr`, on the batch's stream, without synchronisation"""
+        count = self.step_log_count() - first if count is None else count
+        self._chk(self.L.srbm_step_log_copy_dev(self.h, int(first), int(count), C.c_void_p(ptr)))
+
     def synchronize(self):
         self._chk(self.L.srbm_synchronize(self.h))
 
@@ -569,13 +624,9 @@ class BatchMPC:
     def print_stat_line(self, fh, solve_number, time_ms, inst=0):
         """one table row of MPC::PrintStatLineToFile (mpc.cpp:974-989) for instance `inst` from the last solve.  Merit =
         cost + mu * L1 dynamics defect (mpc.cpp:749-757, mu = 5000), Merit dd = its directional derivative along the step."""
-        cw = 15
         st, err = self.status()
-        s = self.stats()[inst]
         merit, merit_dd = self.merit()
-        vals = ['%d' % solve_number, '%g' % time_ms, '%g' % s[2], '%g' % s[3], '%g' % s[0], '%g' % s[1], '%g' % merit[inst], '%g' % merit_dd[inst],
-                SOLVE_TYPE_NAMES.get(int(st[inst]), 'Other'), '%g' % s[1]]       # last column: cost_ = GetCostValue(prev_qp_sol), the same value as 'Cost' (mpc.cpp:809, msrb.cpp:183-184)
-        fh.write(''.join(v.ljust(cw) for v in vals) + '\n')
+        fh.write(format_stat_line(solve_number, time_ms, self.stats()[inst], merit[inst], merit_dd[inst], st[inst]))
 
     # ---- measurement aids ----
     def enable_kernel_timing(self, max_launches):

@@ -144,6 +144,43 @@ int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int subs
 int srbm_synchronize(srbm_batch* h);
 void* srbm_stream(srbm_batch* h);            /* hipStream_t the kernels are launched on */
 
+/* ---- the step log: every step of a multi-step launch, kept on the device ----
+ * A K-step launch leaves only its LAST solve in the read-back entries (status, stats, QP cost, merit, solve flags, plant state, the trajectory).
+ * With a log enabled, every solve of srbm_rti_advance, srbm_closed_loop_advance (both launch forms), srbm_rti_advance_unfused and
+ * srbm_get_real_time_update[_dev] also writes one record per instance, with no host round trip: the multi-step kernels write it after the update
+ * phase of each step, the one-step entries through one small kernel behind their four.  srbm_create_initial_run, the srbm_gait_* entries and the
+ * line-search candidates never log.  Logging changes no result (tests/test_gpu_step_log.py: bitwise).
+ * The log is log[slot][batch][SRBM_STEP_LOG_DOUBLES]; a call of `steps` steps fills the slots [cursor, cursor + steps) and moves the cursor.  One
+ * record, integers stored as doubles:
+ *     index     content                                                                   the one-step read-back it equals
+ *     0         the instance's solve count after this solve (the 'Solve #' column)
+ *     1         init_time handed to the solve
+ *     2, 3, 4   status, error bits of this solve, solve flags                             srbm_get_status, srbm_get_solve_flags
+ *     5, 6      n, m                                                                      srbm_get_sizes columns 0, 1
+ *     7..14     alpha, cost, dynamics defect, step norm, IPM iterations,                  srbm_get_stats, in its order
+ *               primal residual, dual residual, gap
+ *     15, 16    QP cost, merit dd                                                         srbm_get_qp_cost, srbm_get_merit (merit_dd)
+ *     17..29    the state handed to the solve [13]: under a plant its state after         srbm_plant_get_state
+ *               integration and push, open loop node 1 of the previous trajectory
+ *     30..41    the foot locations handed to the solve [4][3]
+ *     42..53    Trajectory::GetForce(ee, init_time) of the NEW trajectory [4][3]          srbm_eval_trajectory at init_time
+ *     54..57    the contact flags of the new trajectory at init_time [4]                  srbm_eval_trajectory at init_time
+ *     58..63    reserved, 0
+ * The merit is not a field: it is cost + 5000 * defect (fields 8 and 9) formed on the host, as srbm_get_merit forms it.  The evaluation behind
+ * 42..57 reads the instance only (its error bits stay as the solve left them); a foot whose spline lookup fails gets NaN forces and flag -1.
+ * srbm_step_log_enable allocates max_steps x batch records and sets the cursor to 0; max_steps = 0 disables logging and frees the buffer.  A call
+ * whose steps do not fit the remaining capacity fails before anything is launched (srbm_last_error says how much room there is) and leaves the
+ * batch untouched.  srbm_step_log_get (host, synchronous: out[count][batch][64]) and srbm_step_log_copy_dev (device to device on the batch's
+ * stream, no synchronisation) fail for a slot range outside [0, steps_logged) and when no log is enabled.  A clone has logging off.
+ * srbm_debug_get_launch_info reports a logged launch by the code of its unlogged twin. */
+#define SRBM_STEP_LOG_DOUBLES 64
+int srbm_step_log_record_doubles(void);                          /* SRBM_STEP_LOG_DOUBLES; callable without a GPU */
+int srbm_step_log_enable(srbm_batch* h, int max_steps);
+int srbm_step_log_reset(srbm_batch* h);                          /* cursor 0, buffer kept */
+int srbm_step_log_count(srbm_batch* h, int* steps_logged);
+int srbm_step_log_get(srbm_batch* h, int first_slot, int count, double* out);
+int srbm_step_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev);
+
 /* ---- mpc::Trajectory as a flat record (mpc/include/trajectory.h:20-175): what MPC::GetTrajectory returns by value and
  * MPC::SetWarmStartTrajectory takes.  Knot tables as srbm_get_knots: kind 0 lift-off, 1 touch-down, 2 stance-interior
  * (force node with value + slope/FORCE_MULT), 3 mid-swing; force[ee][coord][knot] = {value, slope/100} (used on kind-2
@@ -318,7 +355,8 @@ int srbm_get_sizes(srbm_batch* h, int* sizes);
  * queue ran out (multi-step launches of a batch larger than the chip hand out (instance, step) items to a resident grid; never observed). */
 int srbm_get_status(srbm_batch* h, int* status, int* err);
 /* Sticky accumulators over every solve since creation / the last clear (multi-step launches overwrite status and err each
- * step): acc[batch][4] = {all error bits raised, solves, solves not in {Solved, SolvedInacc}, of those MaxIter} */
+ * step; the step log, srbm_step_log_*, keeps both per step): acc[batch][4] = {all error bits raised, solves, solves not in {Solved, SolvedInacc},
+ * of those MaxIter} */
 int srbm_get_status_accumulated(srbm_batch* h, int* acc);
 int srbm_clear_status_accumulators(srbm_batch* h);
 /* counters over the same span: c[4] = {solves, solves ended by the step rule, lower-start attempts, attempts repeated from the standard start} */
