@@ -46,6 +46,9 @@ KMAX, NODES_MAX = 32, 101
 # srbm_set_solver_step_rule: a new batch runs every solve to the reference's gap criterion (0, 0); these are the values bench.py opts into for
 # its headline line (include/srbm_rti.h: SRBM_FAST_TOL_STEP, SRBM_FAST_START_MU)
 FAST_TOL_STEP, FAST_START_MU = 1e-5, 0.1
+# srbm_set_solver_tolerances(gap_abs, gap_rel, feas, max_iter): ClarabelInterface's settings (clarabel_interface.cpp:165-175), which are also what
+# a new batch holds (srbm_batch_create).  srbm_loader re-exports the name as workloads.REFERENCE_SOLVER_SETTINGS
+REFERENCE_SOLVER_SETTINGS = (1e-15, 1e-15, 1e-10, 200)
 
 
 class Trajectory(C.Structure):       # srbm_trajectory: mpc::Trajectory as a flat record (include/srbm_rti.h)
@@ -308,6 +311,25 @@ class BatchMPC:
                 if (k in c) != (k in c0) or (k in c and not _same(c[k], c0[k])):
                     raise ValueError('from_configs: config %d: %s differs from config 0 (it is batch-wide: one value for every instance)' % (i, k))
         return cls(c0, len(cfgs), device=device, large=large, _cfgs=cfgs)
+
+    @classmethod
+    def cold_start(cls, cfg, states, ees, mode=None, large=None, device=0, initial_run=True):
+        """The cold start of the tests and the developer scripts in one call: a batch of len(states) instances of cfg (a list of cfgs: from_configs),
+        warm-started at `states`, at the reference's solver settings, with the step rule `mode` = (tol_step, start_mu) (None: a new batch keeps
+        the library's (0, 0)), after create_initial_run(states, ees) unless initial_run is false.  The three setters write disjoint fields, so a
+        caller that needs something between them and the initial run passes initial_run=False and goes on from there.  (bench.py does not use
+        this: it keeps its own three copies of the sequence, so that what it measures is written out in the file that measures it.)"""
+        if isinstance(cfg, (list, tuple)):
+            g = cls.from_configs(cfg, device=device, large=large)
+        else:
+            g = cls(cfg, len(np.asarray(states, dtype=np.float64).reshape(-1, 13)), device=device, large=large)
+        g.set_state_trajectory_warm_start(states)
+        g.set_solver_tolerances(*REFERENCE_SOLVER_SETTINGS)
+        if mode is not None:
+            g.set_solver_step_rule(*mode)
+        if initial_run:
+            g.create_initial_run(states, ees)
+        return g
 
     def instance_model(self, inst):
         """srbm_get_instance_model: (srbm_mpc_info, srbm_model) of instance inst"""

@@ -2,6 +2,13 @@
 a global batch over ranks (section 8e).  Used by bench.py, by the parity tests (the same seeded instances) and by the developer scripts."""
 import numpy as np
 
+# REFERENCE_SOLVER_SETTINGS -- (gap_abs, gap_rel, feas, max_iter) of srbm_set_solver_tolerances -- is defined once, in host.py beside the setter;
+# srbm_loader hands it to this module under the same name (the two modules do not import each other)
+
+# the nominal feet of the reference's simulation (test/simulation_mpc.cpp:104-108): FL FR RL RR
+EE_NOMINAL = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
+EE_NOMINAL.setflags(write=False)           # one array for every caller
+
 
 def shard_range(total, rank, world):
     """contiguous block [lo, hi) of `total` instances owned by `rank`"""
@@ -10,6 +17,16 @@ def shard_range(total, rank, world):
     lo = rank * per + min(rank, rem)
     return lo, lo + per + (1 if rank < rem else 0)
 
+
+def instances(cfg, make_inst, ids):
+    """the seeded instances `ids` of a generator (config_b_instance, ...) as one batch: (states [B, 13], ees [B, 12]), contiguous float64.
+    ids: an int B for range(B), or any iterable of instance numbers; cfg: one dict, or a list with one dict per instance (a heterogeneous batch)"""
+    ids = list(range(ids)) if isinstance(ids, (int, np.integer)) else list(ids)
+    cfgs = cfg if isinstance(cfg, (list, tuple)) else [cfg] * len(ids)
+    if len(cfgs) != len(ids):
+        raise ValueError('instances: %d configs for %d instances' % (len(cfgs), len(ids)))
+    states, ees = zip(*[make_inst(c, b) for c, b in zip(cfgs, ids)])
+    return np.ascontiguousarray(states, dtype=np.float64), np.ascontiguousarray(ees, dtype=np.float64).reshape(len(ids), 12)
 
 
 def config_b_instance(cfg, b):
@@ -52,8 +69,7 @@ def config_d_instance(cfg, b):
     state = np.array(cfg['srb_init'], float)
     state[3] += tnorm(2.5); state[4] += tnorm(2.5)
     state[12] += rng.normal(0.0, 0.2)
-    ee = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)      # test/simulation_mpc.cpp:104-108
-    return state, ee
+    return state, EE_NOMINAL.copy()
 
 
 def heterogeneous_configs(base, q_diags, B, seed=4242, num_nodes=None):

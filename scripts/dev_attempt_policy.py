@@ -11,10 +11,9 @@ from srbm_loader import host, workloads
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 105
 cfg = host.load_config()
 B = 256
-st, ee = zip(*[workloads.config_b_instance(cfg, b) for b in range(B)])
-st, ee = np.array(st), np.array(ee).reshape(B, 12)
+st, ee = workloads.instances(cfg, workloads.config_b_instance, B)
 def run(mu):
-    g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_step_rule(0.0, mu)
+    g = host.BatchMPC.cold_start(cfg, st, ee, mode=(0.0, mu), initial_run=False)
     for _ in range(10): g.create_initial_run(st, ee)
     def totals():
         out = np.zeros(B); g._chk(g.L.srbm_debug_get_instance_iters(g.h, out.ctypes.data_as(C.POINTER(C.c_double)))); return out

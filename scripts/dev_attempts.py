@@ -11,10 +11,8 @@ mu = float(sys.argv[2]) if len(sys.argv) > 2 else 0.1
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 60
 cfg = host.load_config()
 B = 256
-st, ee = zip(*[workloads.config_b_instance(cfg, b) for b in range(B)])
-st, ee = np.array(st), np.array(ee).reshape(B, 12)
-g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200); g.set_solver_step_rule(ts, mu)
-g.create_initial_run(st, ee)
+st, ee = workloads.instances(cfg, workloads.config_b_instance, B)
+g = host.BatchMPC.cold_start(cfg, st, ee, mode=(ts, mu))
 prev_it = g.work_counters()[0]
 tot = np.zeros(B)
 print('mode', g.solver_step_rule())

@@ -13,9 +13,8 @@ ts = float(sys.argv[1]) if len(sys.argv) > 1 else 0.0
 mu = float(sys.argv[2]) if len(sys.argv) > 2 else 0.1
 cfg = host.load_config('a1_config_distr_rejection')
 B, CUS = 512, 256
-st, ee = zip(*[workloads.config_d_instance(cfg, b) for b in range(B)])
-st, ee = np.array(st), np.array(ee).reshape(B, 12)
-g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_step_rule(ts, mu)
+st, ee = workloads.instances(cfg, workloads.config_d_instance, B)
+g = host.BatchMPC.cold_start(cfg, st, ee, mode=(ts, mu), initial_run=False)
 for _ in range(10): g.create_initial_run(st, ee)
 def totals():
     out = np.zeros(B)

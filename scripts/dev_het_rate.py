@@ -12,11 +12,8 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 cfg = host.load_config()
 het = workloads.heterogeneous_configs(cfg, [cfg['Q_srbd_diag'], host.load_config('a1_config_distr_rejection')['Q_srbd_diag']], B)
 for name, cfgs in (('uniform', [cfg] * B), ('heterogeneous', het)):
-    states, ees = zip(*[workloads.config_b_instance(c, b) for b, c in enumerate(cfgs)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B) if name == 'uniform' else host.BatchMPC.from_configs(cfgs)
-    g.set_state_trajectory_warm_start(states); g.set_solver_step_rule(0.0, 0.1)
-    g.create_initial_run(states, ees)
+    states, ees = workloads.instances(cfgs, workloads.config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg if name == 'uniform' else cfgs, states, ees, mode=(0.0, 0.1))
     g.rti_advance(0, 5); g.synchronize()
     w = []
     for k in range(5):

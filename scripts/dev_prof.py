@@ -9,12 +9,9 @@ cfg = host.load_config(sys.argv[1] if len(sys.argv) > 1 else 'a1_configuration')
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 s0 = np.array(cfg['srb_init'], float)
 ee = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-gb = host.BatchMPC(cfg, B); gb.set_state_trajectory_warm_start(s0)
 mode = os.environ.get('PROF_MODE', 'lower_start')      # the mode bench.py's headline runs (round 5); 'step_rule' / 'ref' for the others
-if mode == 'lower_start':
-    gb.enable_lower_start()
-elif mode == 'step_rule':
-    gb.enable_fast_termination()
+gb = host.BatchMPC.cold_start(cfg, [s0] * B, ee, mode={'lower_start': (0.0, host.FAST_START_MU), 'step_rule': (host.FAST_TOL_STEP, host.FAST_START_MU)}.get(mode),
+                              initial_run=False)
 print('solver settings', gb.solver_step_rule())
 
 name, group = C.c_char_p(), C.c_char_p()

@@ -5,10 +5,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from srbm_loader import host
-import test_gpu_wbc as T
+from gpu_kit import wbc_inputs
 
 B = 256
-cfg, q, v, q_des, v_des, rng = T.make(B, seed=9)
+cfg, q, v, q_des, v_des, rng = wbc_inputs(B, seed=9)
 contact = np.array([[[1, 0, 0, 1], [0, 1, 1, 0], [1, 1, 1, 0]][b % 3] for b in range(B)], np.int32)
 fdes = np.zeros((B, 12))
 for b in range(B):

@@ -8,9 +8,8 @@ if len(sys.argv) > 1 and sys.argv[1] == '--child':
     from srbm_loader import host, workloads
     B, L, K, ts, mu = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), float(sys.argv[5]), float(sys.argv[6])
     cfg = host.load_config('a1_config_distr_rejection')
-    st, ee = zip(*[workloads.config_d_instance(cfg, b % 512) for b in range(B)])
-    st, ee = np.array(st), np.array(ee).reshape(B, 12)
-    g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_step_rule(ts, mu)
+    st, ee = workloads.instances(cfg, workloads.config_d_instance, [b % 512 for b in range(B)])
+    g = host.BatchMPC.cold_start(cfg, st, ee, mode=(ts, mu), initial_run=False)
     for _ in range(10): g.create_initial_run(st, ee)
     rec = []
     plan = [(0, 5), (5, 20), (25, 20), (45, 20), (65, 20), (85, 20), (5, 40)] if K == 0 else [(l * K, K) for l in range(L)]

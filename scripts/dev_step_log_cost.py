@@ -35,13 +35,9 @@ def timed_launch(base, closed, steps, logged):
 
 
 def protocol(name, cfg, make_inst, B, steps, closed):
-    states, ees = zip(*[make_inst(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    base = host.BatchMPC(cfg, B)
-    base.set_state_trajectory_warm_start(states)
-    if not closed:
-        base.enable_lower_start()                               # the bench's mode; under a plant the library makes no lower-start attempt
-    base.create_initial_run(states, ees)
+    states, ees = workloads.instances(cfg, make_inst, B)
+    # open loop: the bench's mode (lower start); under a plant the library makes no lower-start attempt
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=None if closed else (0.0, host.FAST_START_MU))
     if closed:
         base.plant_set_state(states)
         rng = np.random.default_rng(777)

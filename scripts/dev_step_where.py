@@ -10,8 +10,7 @@ first = int(sys.argv[2]) if len(sys.argv) > 2 else 56
 count = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 cfg = host.load_config()
 s0, ee = workloads.config_b_instance(cfg, b)
-g = host.BatchMPC(cfg, 1); g.set_state_trajectory_warm_start(s0); g.set_solver_step_rule(0.0, 0.1)
-g.create_initial_run(s0, ee)
+g = host.BatchMPC.cold_start(cfg, s0, ee, mode=(0.0, 0.1))
 NU = g.NUMAX
 for i in range(first + count):
     g.rti_advance(i, 1); g.synchronize()

@@ -8,9 +8,7 @@ from srbm_loader import workloads as bench
 cfg = host.load_config()
 b = int(sys.argv[1]) if len(sys.argv) > 1 else 11
 s0, ee = bench.config_b_instance(cfg, b)
-g = host.BatchMPC(cfg, 1); g.set_state_trajectory_warm_start(s0)
-if 'AB_STEP' in os.environ: g.set_solver_step_rule(float(os.environ['AB_STEP']), float(os.environ.get('AB_MU', 0)))
-g.create_initial_run(s0, ee)
+g = host.BatchMPC.cold_start(cfg, s0, ee, mode=(float(os.environ['AB_STEP']), float(os.environ.get('AB_MU', 0))) if 'AB_STEP' in os.environ else None)
 nsteps = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 for i in range(nsteps):
     g.rti_advance(i, 1)

@@ -28,10 +28,8 @@ from srbm_loader import host
 from srbm_loader import workloads
 cfg = host.load_config()
 B = 256
-states, ees = zip(*[workloads.config_b_instance(cfg, b) for b in range(B)])
-states, ees = np.array(states), np.array(ees).reshape(B, 12)
-g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(states)
-g.set_solver_step_rule(0.0, 0.1)
+states, ees = workloads.instances(cfg, workloads.config_b_instance, B)
+g = host.BatchMPC.cold_start(cfg, states, ees, mode=(0.0, 0.1), initial_run=False)
 for _ in range(10): g.create_initial_run(states, ees)
 g.rti_advance(0, 5); g.synchronize()
 g.rti_advance_unfused(5, STEPS); g.synchronize()

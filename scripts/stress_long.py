@@ -12,10 +12,8 @@ mu = float(sys.argv[4]) if len(sys.argv) > 4 else 0.1
 cfg = host.load_config() if wl == 'B' else host.load_config('a1_config_distr_rejection')
 B = 256 if wl == 'B' else 512
 inst = workloads.config_b_instance if wl == 'B' else workloads.config_d_instance
-st, ee = zip(*[inst(cfg, b) for b in range(B)])
-st, ee = np.array(st), np.array(ee).reshape(B, 12)
-g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200); g.set_solver_step_rule(ts, mu)
-g.create_initial_run(st, ee)
+st, ee = workloads.instances(cfg, inst, B)
+g = host.BatchMPC.cold_start(cfg, st, ee, mode=(ts, mu))
 g.clear_status_accumulators()
 t0 = time.perf_counter()
 for k in range(0, steps, 50):

@@ -16,5 +16,6 @@ def _load(name, file):
 
 host = _load('srbm_host', 'host.py')
 workloads = _load('srbm_workloads', 'workloads.py')
+workloads.REFERENCE_SOLVER_SETTINGS = host.REFERENCE_SOLVER_SETTINGS       # one definition (host.py), reachable from both
 sys.modules[__name__ + '.workloads'] = workloads          # `from srbm_loader.workloads import ...`
 sys.modules[__name__ + '.host'] = host

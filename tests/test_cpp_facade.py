@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from srbm_loader import host
+from srbm_loader.workloads import EE_NOMINAL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # <Eigen/Core> for the facade headers: the system's if there is one, else the stand-in of the tests (this container has no Eigen)
@@ -69,10 +70,8 @@ def test_cpp_host_side_equals_ctypes_path(tmp_path):
         vals.setdefault(k, []).append(float(v))
     # the same sequence through ctypes
     s0 = np.array(cfg['srb_init'], float)
-    ee0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-    g = host.BatchMPC(cfg, 2)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    ee0 = EE_NOMINAL
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, ee0, initial_run=False)
     assert g.solver_step_rule() == (0.0, 0.0)
     g.create_initial_run(s0, ee0)
     g.rti_advance(0, 4); g.synchronize()
@@ -225,10 +224,8 @@ def test_mpc_facade_runs_the_controller_protocol_like_the_ctypes_path(tmp_path):
     assert log[0] == '-' * 150 and 'MPC Statistics' in log[1] and log[2].startswith('MPC started at: ') and log[3] == 'Number of nodes: 20'
     assert len([l for l in log if l[:1].isdigit()]) == TICKS and all(len(l.rstrip()) <= 150 for l in log)
     s0 = np.array(cfg['srb_init'], float)
-    ee0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-    g = host.BatchMPC(cfg, 1)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_step_rule(0.0, 0.0)                # as mpc::MPCSingleRigidBody of the facade does (gap criterion for every solve)
+    ee0 = EE_NOMINAL
+    g = host.BatchMPC.cold_start(cfg, s0, None, mode=(0.0, 0.0), initial_run=False)    # as mpc::MPCSingleRigidBody of the facade does (gap criterion for every solve)
     g.add_force_cost(cfg['force_cost'])
     g.create_initial_run(s0, ee0)
     gait = host.BatchGaitOptimizer(g)
@@ -335,9 +332,7 @@ def test_row_f3_facade_runs_the_control_tick_like_the_ctypes_path(tmp_path):
     assert vals['tick_status'] == [0.0] * TICKS and vals['run_num'] == [float(TICKS)]
     s0 = np.array(cfg['srb_init'], float)
     q0 = np.array(gold['source']['init_config'], float)
-    g = host.BatchMPC(cfg, 1)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_step_rule(0.0, 0.0)                # as mpc::MPCSingleRigidBody of the facade does (gap criterion for every solve)
+    g = host.BatchMPC.cold_start(cfg, s0, None, mode=(0.0, 0.0), initial_run=False)    # as mpc::MPCSingleRigidBody of the facade does (gap criterion for every solve)
     g.add_force_cost(cfg['force_cost'])
     ee0 = g.forward_kinematics(q0)[0]
     ee0[:, 2] = 0
@@ -411,10 +406,8 @@ def test_playground_protocol_and_the_reference_partials_test_through_the_facade(
     assert vals['qp_same_size'] == [1.0] * ITER and len(set(vals['qp_n'])) == 1 and vals['qp_n'][0] == 372.0
     # (3) the same protocol through ctypes
     s0 = np.array(cfg['srb_init'], float)
-    ee0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-    g = host.BatchMPC(cfg, 1)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_step_rule(0.0, 0.0)
+    ee0 = EE_NOMINAL
+    g = host.BatchMPC.cold_start(cfg, s0, None, mode=(0.0, 0.0), initial_run=False)
     g.add_force_cost(cfg['force_cost'])
     g.create_initial_run(s0, ee0)
     gait = host.BatchGaitOptimizer(g)

@@ -7,16 +7,12 @@ trajectories <= 1e-4 relative (the north-star tolerance; a plant step alone agre
 import numpy as np
 import pytest
 
+from gpu_kit import REL_TOL, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance, config_d_instance
+from srbm_loader.workloads import config_b_instance, config_d_instance, instances
 
 pytestmark = pytest.mark.gpu
-REL_TOL = 1e-4
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def oracle_closed_loop(cfg, state, ee, steps, substeps, advance_time, push_time, impulse):
@@ -39,12 +35,10 @@ def oracle_closed_loop(cfg, state, ee, steps, substeps, advance_time, push_time,
 def test_closed_loop_rollout_matches_oracle(advance_time):
     cfg = load_config()
     B, K, SUB = 3, 6, 5
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     push_time = np.array([0.12, 0.07, 1e9])                      # instance 2 is never pushed
     impulse = np.array([[2.5, -1.0, 0.3, 0.05, -0.1, 0.2], [-1.5, 2.0, 0.0, 0.0, 0.1, -0.1], [9, 9, 9, 9, 9, 9]], float)
-    g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(states); g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.create_initial_run(states, ees)
+    g = host.BatchMPC.cold_start(cfg, states, ees)
     g.plant_set_state(states); g.plant_set_push(push_time, impulse)
     for i in range(K):                                           # one step per call: the plant state after every step is compared
         g.closed_loop_advance(i, 1, SUB, advance_time); g.synchronize()
@@ -67,13 +61,12 @@ def test_closed_loop_fused_steps_equal_single_steps_and_push_distribution():
     instance) runs without error bits and stays finite"""
     cfg = load_config()
     B, K = 8, 6
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     rng = np.random.default_rng(5)
     pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
     res = []
     for one_launch in (True, False):
-        g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(states); g.create_initial_run(states, ees)
+        g = host.BatchMPC.cold_start(cfg, states, ees)
         g.plant_set_state(states); g.plant_set_push(pt, imp)
         if one_launch:
             g.closed_loop_advance(0, K, 4, True)
@@ -90,9 +83,8 @@ def test_closed_loop_fused_steps_equal_single_steps_and_push_distribution():
     # Config D sizes
     cfgd = load_config('a1_config_distr_rejection')
     B = 16
-    states, ees = zip(*[config_d_instance(cfgd, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfgd, B); g.set_state_trajectory_warm_start(states); g.create_initial_run(states, ees)
+    states, ees = instances(cfgd, config_d_instance, B)
+    g = host.BatchMPC.cold_start(cfgd, states, ees)
     g.plant_set_state(states)
     g.plant_set_push(rng.uniform(0.0, 0.1, B), rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.3, 0.1, 0.1, 0.2]))
     g.closed_loop_advance(0, 10, 4, True); g.synchronize()

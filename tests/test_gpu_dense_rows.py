@@ -9,11 +9,11 @@ error bits), and a K-step launch against its one-step launches, bit for bit (tes
 import numpy as np
 import pytest
 
+from gpu_kit import REL_TOL
+from gpu_protocols import resync_protocol, run_case
 from oracle_py import first_rti_sizes, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance, config_d_instance
-from test_gpu_launch_equivalence import run_case
-from test_gpu_resync import EE0, REL_TOL, resync_protocol
+from srbm_loader.workloads import EE_NOMINAL, config_b_instance, config_d_instance, instances
 
 pytestmark = pytest.mark.gpu
 # Contact times 0.22 s apart on Config D's horizon: at or above the gait LP's lower bound on a phase (MIN_TIME = 0.2), so the gait step can
@@ -31,11 +31,6 @@ def placements(N, shapes, large=False):
 def device_shapes(r):
     """(n, n_force) of every instance after every step of a run_case chain (srbm_get_sizes: columns 0 and 4)"""
     return {(int(sz[b, 0]), int(sz[b, 4])) for sz in r['sizes'] for b in range(sz.shape[0])}
-
-
-def instances(cfg, make, B):
-    states, ees = zip(*[make(cfg, b) for b in range(B)])
-    return np.array(states), np.array(ees)
 
 
 def set_phases(g, phase):
@@ -151,11 +146,8 @@ def test_large_build_capacity_overflow_fails_loudly():
     nu, _, _ = first_rti_sizes(cfg, PHASE_OVERFLOW)
     assert nu == 288 and nu > host.lib(True).capacity['nu']
     s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC(cfg, 2, large=True)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.create_initial_run(s0, EE0)
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, large=True)
     set_phases(g, PHASE_OVERFLOW)
-    g.get_real_time_update(s0, 0.0, EE0)
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL)
     st, err = g.status()
     assert np.all(err & 16) and np.all(st == 8), (st, err)

@@ -4,16 +4,12 @@ argmin index exact, costs / trajectories <= 1e-4 relative."""
 import numpy as np
 import pytest
 
+from gpu_kit import REL_TOL, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
+from srbm_loader.workloads import EE_NOMINAL, config_c_instance, instances
 
 pytestmark = pytest.mark.gpu
-REL_TOL = 1e-4
-EE0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def run_pair(cfgname, nsteps, batch=2, tol=1e-15):
@@ -26,9 +22,9 @@ def run_pair(cfgname, nsteps, batch=2, tol=1e-15):
     g.set_solver_step_rule(0.0, 0.0)        # the caller drives the protocol here: the solves it differentiates run to the gap criterion (include/srbm_rti.h)
     o = OracleMPC(cfg)
     o.set_warmstart(s0)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
     dt = cfg['integrator_dt']
-    state, ee, t = s0, EE0, 0.0
+    state, ee, t = s0, EE_NOMINAL, 0.0
     for i in range(nsteps):
         t = i * dt
         state = o.states()[1]
@@ -253,13 +249,10 @@ def test_controller_loop_with_gait_step(cfgname, runs, knot_tol, resync):
     F = 5
     cfg = load_config(cfgname)
     s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC(cfg, 2)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.set_solver_step_rule(0.0, 0.0)
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=(0.0, 0.0))
     o = OracleMPC(cfg)
     o.set_warmstart(s0)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    o.initial_run(s0, EE_NOMINAL)
     gait = host.BatchGaitOptimizer(g)
     dt = cfg['integrator_dt']
     ready = False
@@ -316,21 +309,17 @@ def seeded_batch_of_32():
     """BASELINE config 3 as the bench runs it (a1_gait_opt_config values at N = 20, dt = 0.05): 32 DIFFERENT seeded instances, each re-synchronised to
     its own oracle before every RTI step, after four steps (all solves at the gap criterion: the default of a new batch)"""
     from concurrent.futures import ThreadPoolExecutor
-    from srbm_loader.workloads import config_c_instance
     cfg = load_config('a1_gait_opt_config', num_nodes=20, integrator_dt=0.05)
     B, NSTEPS = 32, 4
-    states, ees = zip(*[config_c_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    states, ees = instances(cfg, config_c_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, initial_run=False)
     assert g.solver_step_rule() == (0.0, 0.0)
     os_ = []
     for b in range(B):
         o = OracleMPC(cfg); o.set_warmstart(states[b]); os_.append(o)
     pool = ThreadPoolExecutor(16)
     list(pool.map(lambda b: os_[b].initial_run(states[b], ees[b].reshape(4, 3)), range(B)))
-    g.create_initial_run(states, ees.reshape(B, 12))
+    g.create_initial_run(states, ees)
     dt = cfg['integrator_dt']
     for i in range(NSTEPS):
         t = i * dt

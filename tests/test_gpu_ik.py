@@ -10,7 +10,7 @@ import pytest
 
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance
+from srbm_loader.workloads import config_b_instance, instances
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'oracle'))
@@ -76,8 +76,7 @@ def test_targets_from_trajectory_match_the_oracle():
     """MPCController::GetTargetsFromTraj (mpc_controller.cpp:414-511) on the trajectories of a running batch"""
     B = 8
     cfg, legs, q0, g = setup(B)
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     g.set_state_trajectory_warm_start(states)
     g.create_initial_run(states, ees)
     g.rti_advance(0, 3); g.synchronize()
@@ -103,8 +102,7 @@ def test_targets_from_trajectory_match_the_oracle():
 def test_full_batch_targets_properties():
     B = 256
     cfg, legs, q0, g = setup(B)
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     g.set_state_trajectory_warm_start(states)
     g.create_initial_run(states, ees)
     g.rti_advance(0, 2); g.synchronize()
@@ -125,8 +123,7 @@ def test_target_failures_agree_with_the_oracle():
     throws "IK did not converge."): the device reports exactly the instances the numpy restatement fails on, and equal targets on the others"""
     B = 256
     cfg, legs, q0, g = setup(B)
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     g.set_state_trajectory_warm_start(states)
     g.create_initial_run(states, ees)
     g.rti_advance(0, 7); g.synchronize()

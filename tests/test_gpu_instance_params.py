@@ -17,13 +17,13 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from gpu_kit import REL_TOL, assert_rows_bitwise, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance, heterogeneous_configs
+from srbm_loader.workloads import config_b_instance, heterogeneous_configs, instances
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REL_TOL = 1e-4
 FULL_Q_INST = 3          # the instance of a heterogeneous set whose tracking and final costs are a full SPD matrix
 
 
@@ -41,8 +41,7 @@ def full_q(cfg):
 
 
 def inputs(cfgs):
-    st, ee = zip(*[config_b_instance(c, b) for b, c in enumerate(cfgs)])
-    return np.array(st), np.array(ee).reshape(len(cfgs), 12)
+    return instances(cfgs, config_b_instance, len(cfgs))
 
 
 def setup(g, mode, states, ees, full=()):
@@ -53,7 +52,7 @@ def setup(g, mode, states, ees, full=()):
         g.set_quadratic_final_cost_each(k, Q[None])
         g.set_linear_final_cost_each(k, (-1 * Q @ des)[None])
     g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    g.set_solver_tolerances(*host.REFERENCE_SOLVER_SETTINGS)
     g.set_solver_step_rule(*mode)
     g.create_initial_run(states, ees)
 
@@ -83,17 +82,6 @@ def snap(g):
     tr = g.get_trajectory()
     out['trajectory'] = np.array([np.frombuffer(bytes(t), np.uint8) for t in tr])
     return out
-
-
-def assert_rows_bitwise(a, ia, b, ib, where):
-    for k in a:
-        ra, rb = np.asarray(a[k][ia]), np.asarray(b[k][ib])
-        if ra.tobytes() != rb.tobytes():
-            raise AssertionError('%s: %s differs (instance %d against its batch of one)' % (where, k, ia))
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 # ---- 1. batch of one equivalence ----
@@ -164,8 +152,7 @@ def test_heterogeneous_batch_matches_its_oracles_on_identical_inputs():
     B, steps = 32, 12
     cfgs = het_configs(B)
     states, ees = inputs(cfgs)
-    g = host.BatchMPC.from_configs(cfgs)          # (the oracle takes a diagonal Q: no full-Q instance here)
-    setup(g, (0.0, 0.0), states, ees)
+    g = host.BatchMPC.cold_start(cfgs, states, ees, mode=(0.0, 0.0))          # (the oracle takes a diagonal Q: no full-Q instance here)
     oracles = [OracleMPC(c) for c in cfgs]
     for b, o in enumerate(oracles):
         o.set_warmstart(states[b])

@@ -6,17 +6,12 @@ restatement' (SURVEY.md Config E)."""
 import numpy as np
 import pytest
 
+from gpu_kit import REL_TOL, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance
+from srbm_loader.workloads import EE_NOMINAL, config_b_instance, instances
 
 pytestmark = pytest.mark.gpu
-REL_TOL = 1e-4
-EE0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def test_capacities():
@@ -29,15 +24,12 @@ def test_large_build_equals_standard_build_on_config_b():
     blocks differ with the tile distribution, nothing else)"""
     cfg = load_config()
     B = 8
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     res = []
     for large in (False, True):
-        g = host.BatchMPC(cfg, B, large=large)
-        g.set_state_trajectory_warm_start(states)
-        g.set_solver_step_rule(0.0, 0.0)          # fourteen consecutive solves on each build's own path: compared at the gap criterion (rounding-level
-                                                  # differences between the builds must not decide in which iteration a tolerance-based rule fires)
-        g.create_initial_run(states, ees)
+        # fourteen consecutive solves on each build's own path: compared at the gap criterion (rounding-level differences between the builds
+        # must not decide in which iteration a tolerance-based rule fires)
+        g = host.BatchMPC.cold_start(cfg, states, ees, mode=(0.0, 0.0), large=large)
         g.rti_advance(0, 4); g.synchronize()
         st, err = g.status()
         assert np.all(err == 0) and np.all(st <= 1)
@@ -52,11 +44,8 @@ def test_large_build_equals_standard_build_on_config_b():
 def test_n40_horizon_share_of_128_against_the_oracle():
     cfg = load_config(num_nodes=40)                      # dt = 0.05: a 2 s horizon, three more phases per foot
     B = 128
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B, large=True)
-    g.set_state_trajectory_warm_start(states)
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, large=True)
     sample = [0, 17, 64, 127]
     oracles = []
     for b in sample:
@@ -103,10 +92,8 @@ def test_short_phase_schedule_runs_in_the_large_build():
     enforced by the gait LP, not by the MPC); it needs more than 160 variables"""
     cfg = load_config()
     s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC(cfg, 2, large=True)
-    g.set_state_trajectory_warm_start(s0)
-    o = OracleMPC(cfg); o.set_warmstart(s0)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, large=True)
+    o = OracleMPC(cfg); o.set_warmstart(s0); o.initial_run(s0, EE_NOMINAL)
     ct = [o.contact_times(e)[0] for e in range(4)]
     new = [0.1 * np.arange(len(c)) for c in ct]            # 100 ms phases
     o.set_contact_times(new)
@@ -115,8 +102,8 @@ def test_short_phase_schedule_runs_in_the_large_build():
         arr[:, e, :len(new[e])] = new[e]
     g.update_contact_times(arr)
     g.set_warm_start_trajectory([o.trajectory_record(host)] * 2)
-    g.get_real_time_update(s0, 0.0, EE0)
-    so = o.rti(s0, 0.0, EE0)
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL)
+    so = o.rti(s0, 0.0, EE_NOMINAL)
     st, err = g.status()
     sz, osz = g.sizes()[0], o.sizes()
     assert err[0] == 0 and (sz[0], sz[1]) == (osz['n'], osz['m'])

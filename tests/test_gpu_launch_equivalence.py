@@ -19,100 +19,13 @@ hand-off of an instance between CUs on the step queues cannot differ from what a
 Each case also asserts that it covered what it exists to check: in the start_mu > 0 modes attempts were repeated and the back-off made solves
 skip their attempt (the first steps after a cold start are where attempts fail in a row: docs/history.md, "attempt policies"), and the
 multi-step launches of Config D took the step queues (srbm_debug_get_launch_info) while the one-step chain did not."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
+from gpu_protocols import run_case
 from oracle_py import load_config
-from srbm_loader import host
 from srbm_loader.workloads import config_b_instance, config_d_instance
 
 pytestmark = pytest.mark.gpu
-
-
-def advance(g, closed, first, steps):
-    if closed:
-        g.closed_loop_advance(first, steps)
-    else:
-        g.rti_advance(first, steps)
-
-
-def snapshot(g, closed):
-    st, err = g.status()
-    z, s = g.dual_solution()
-    it = np.zeros(g.batch)
-    g._chk(g.L.srbm_debug_get_instance_iters(g.h, it.ctypes.data_as(C.POINTER(C.c_double))))
-    c = g.solver_counters()
-    out = dict(sizes=g.sizes(), status=st, err=err, acc=g.status_accumulated(), flags=g.solve_flags(),
-               solver_counters=np.array([c['solves'], c['step_rule'], c['low_tried'], c['low_failed']]), work_counters=np.array(g.work_counters()),
-               instance_iters=it, stats=g.stats(), x=g.qp_solution(), x_raw=g.raw_qp_minimiser(), z=z, s=s, states=g.trajectory_states(),
-               trajectory=bytes(g.get_trajectory()))
-    if closed:
-        out['plant'] = g.plant_state()
-    return out
-
-
-def assert_bitwise(a, b, where):
-    for k in a:
-        if isinstance(a[k], bytes):
-            assert a[k] == b[k], '%s: %s differs' % (where, k)
-        elif a[k].tobytes() != b[k].tobytes():
-            diff = (a[k].view(np.uint8) != b[k].view(np.uint8)).reshape(len(a[k]), -1).any(axis=1) if a[k].ndim > 1 else a[k] != b[k]
-            raise AssertionError('%s: %s differs at %s %s' % (where, k, 'instances' if a[k].ndim > 1 else 'entries', np.nonzero(diff)[0][:8].tolist()))
-
-
-def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False, prepare=None):
-    """cold start, then the one-step chain and the split launches from clones of the same state; returns the chain's counter deltas.
-    prepare(batch): called after the cold start (e.g. a contact schedule of its own)"""
-    states, ees = zip(*[make_inst(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    base = host.BatchMPC(cfg, B, large=large)
-    base.set_state_trajectory_warm_start(states)
-    base.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)          # the bench's settings
-    base.set_solver_step_rule(*mode)
-    base.create_initial_run(states, ees)
-    if prepare is not None:
-        prepare(base)
-    if closed:                                                     # the pushes of tests/test_gpu_queue.py
-        base.plant_set_state(states)
-        imp = np.zeros((B, 6)); imp[::7, 0] = 0.4; imp[::11, 1] = -0.3
-        base.plant_set_push(time=np.full(B, 2.5 * cfg['integrator_dt']), impulse=imp)
-    base.synchronize()
-    c0 = base.solver_counters()
-    chain = base.clone()
-    ref = []
-    for i in range(steps):
-        advance(chain, closed, i, 1)
-        chain.synchronize()
-        info = chain.debug_launch_info()
-        assert info['steps'] == 1 and not info['queued'], info
-        ref.append(snapshot(chain, closed))
-    n_cu = info['n_cu']
-    c1 = chain.solver_counters()
-    chain.close()
-    assert all(sum(sp) == steps for sp in splits) and any(len(sp) == 1 for sp in splits)
-    queued_launches = 0
-    for sp in splits:
-        c = base.clone()
-        first = 0
-        for k in sp:
-            advance(c, closed, first, k)
-            c.synchronize()
-            info = c.debug_launch_info()
-            assert info['steps'] == k and info['queued'] == (B > n_cu and k > 1), info
-            queued_launches += info['queued']
-            first += k
-            assert_bitwise(snapshot(c, closed), ref[first - 1], 'split %s, after step %d' % (sp, first))
-        c.close()
-    base.close()
-    d = {k: c1[k] - c0[k] for k in c0}
-    if mode[1] > 0 and not closed:                                 # (no attempts at all otherwise)
-        d['skipped_attempts'] = d['solves'] - d['low_tried']
-    print('launch equivalence B=%d steps=%d mode=%s closed=%d: n_cu %d, multi-step launch kernel %s, queued launches %d, chain counters %s'
-          % (B, steps, mode, closed, n_cu, info['kernel'], queued_launches, d))
-    assert d['solves'] == B * steps
-    return dict(counters=d, n_cu=n_cu, queued_launches=queued_launches, kernel=info['kernel'], sizes=[r['sizes'] for r in ref], err=[r['err'] for r in ref])
 
 
 def assert_attempts_and_back_off(d):

@@ -20,36 +20,28 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from gpu_kit import relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance
+from srbm_loader.workloads import config_b_instance, instances
 
 pytestmark = pytest.mark.gpu
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def own_path_run(fast, B=128, steps=100, mode=None):
     cfg = load_config()
     dt = cfg['integrator_dt']
     nx = (cfg['num_nodes'] + 1) * 12
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    if mode is not None:
-        g.set_solver_step_rule(*mode)
-    elif fast:
-        g.enable_fast_termination()
+    states, ees = instances(cfg, config_b_instance, B)
+    if mode is None and fast:
+        mode = (host.FAST_TOL_STEP, host.FAST_START_MU)
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=mode, initial_run=False)
     oracles = []
     for b in range(B):
         o = OracleMPC(cfg); o.set_warmstart(states[b]); oracles.append(o)
     pool = ThreadPoolExecutor(16)
     list(pool.map(lambda b: oracles[b].initial_run(states[b], ees[b].reshape(4, 3)), range(B)))
-    g.create_initial_run(states, ees.reshape(B, 12))
+    g.create_initial_run(states, ees)
     g.clear_status_accumulators()
     err = np.full((steps, B), np.nan)
     err_states = np.full((steps, B), np.nan)

@@ -9,32 +9,18 @@ Tolerances (BASELINE.json north_star / BASELINE.md section 3.5):
 import numpy as np
 import pytest
 
+from gpu_kit import EE_TEST, REL_TOL, relerr
+from gpu_kit import status_ok_or_bad as status_class
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
+from srbm_loader.workloads import EE_NOMINAL, config_b_instance, config_d_instance, instances
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL = 1e-4          # stated tolerance of the north star
-EE0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)   # test/simulation_mpc.cpp:104-108
-EE_TEST = np.array([[0.1526, 0.12523, 0.011089], [0.1526, -0.12523, 0.011089],
-                    [-0.208321844, 0.1363286, 0.01444], [-0.208321844, -0.1363286, 0.01444]])  # test/mpc_test.cpp:97-101
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
-
-
-def status_class(st):
-    """Solved / SolvedInacc / MaxIter steer MPCSingleRigidBody::Solve identically (msrb.cpp:136-144); which of the three
-    an interior-point code reports at a 1e-15 gap tolerance is solver-internal (Clarabel is unpinned)."""
-    return 'ok' if int(st) in (0, 1, 2) else 'bad'
 
 
 def make_pair(cfg, batch=2, state=None):
     s0 = np.array(cfg['srb_init'], float) if state is None else state
-    g = host.BatchMPC(cfg, batch)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    g = host.BatchMPC.cold_start(cfg, [s0] * batch, None, initial_run=False)
     o = OracleMPC(cfg)
     o.set_warmstart(s0)
     return g, o, s0
@@ -94,8 +80,8 @@ def test_cold_start_and_open_loop_rti_parity(cfgname, nsteps):
     the same measured state / foot positions each step (taken from the oracle trajectory)."""
     cfg = load_config(cfgname)
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0)
-    o.initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL)
+    o.initial_run(s0, EE_NOMINAL)
     dt = cfg['integrator_dt']
     seen = set()
     for i in range(nsteps):
@@ -123,46 +109,21 @@ def test_cold_start_and_open_loop_rti_parity(cfgname, nsteps):
         assert len(seen) >= 3        # sizes are ragged in time (phases enter / leave the horizon)
 
 
-def config_b_instance(cfg, b):
-    """Synthetic instance b of Config B: perturbed initial state and foot positions."""
-    rng = np.random.Generator(np.random.MT19937(20240112 + b))
-    u = lambda lo, hi: lo + (hi - lo) * rng.random()
-    m = cfg['mass']
-    p = np.array([u(-0.02, 0.02), u(-0.02, 0.02), 0.30 + u(-0.01, 0.01)])
-    v = np.array([u(-0.5, 0.5), u(-0.5, 0.5), u(-0.1, 0.1)])
-    rpy = np.array([u(-0.05, 0.05), u(-0.05, 0.05), u(-0.05, 0.05)])
-    L = np.array([u(-0.1, 0.1), u(-0.1, 0.1), u(-0.1, 0.1)])
-    th = np.linalg.norm(rpy)
-    quat = np.concatenate([np.sin(th / 2) / th * rpy, [np.cos(th / 2)]])
-    state = np.concatenate([p, m * v, quat, L])
-    hips = np.array([[0.2055, 0.147], [0.2055, -0.147], [-0.1555, 0.147], [-0.1555, -0.147]])
-    ee = np.zeros((4, 3))
-    for e in range(4):
-        ee[e, 0] = p[0] + hips[e, 0] + u(-0.02, 0.02)
-        ee[e, 1] = p[1] + hips[e, 1] + u(-0.02, 0.02)
-    return state, ee
-
-
 def test_batch_of_distinct_instances_matches_per_instance_oracle():
     cfg = load_config()
     B = 8
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    states, ees = instances(cfg, config_b_instance, B)
     # an OWN-PATH comparison (eleven consecutive solves, each side relinearising around its own previous solution): a statement about the SQP
     # path, which amplifies per-solve differences ~100x along the flat directions -- comparable only when both sides end their solves by the same
     # criterion, the reference's (step rule off; tests/test_gpu_resync.py compares every solve of the default rule on identical QPs)
-    g.set_solver_step_rule(0.0, 0.0)
-    g.create_initial_run(states, ees.reshape(B, 12))
-    g.get_real_time_update(states, 0.0, ees.reshape(B, 12))
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=(0.0, 0.0))
+    g.get_real_time_update(states, 0.0, ees)
     xs = g.qp_solution(); st, err = g.status(); sz = g.sizes(); tr = g.trajectory_states()
     for b in range(B):
         o = OracleMPC(cfg)
         o.set_warmstart(states[b])
-        o.initial_run(states[b], ees[b])
-        so = o.rti(states[b], 0.0, ees[b])
+        o.initial_run(states[b], ees[b].reshape(4, 3))
+        so = o.rti(states[b], 0.0, ees[b].reshape(4, 3))
         n = o.sizes()['n']
         assert sz[b, 0] == n and sz[b, 1] == o.sizes()['m']
         assert status_class(st[b]) == status_class(so) and err[b] == 0
@@ -176,11 +137,8 @@ def test_qp_minimiser_matches_reference_solver_on_the_same_qp():
     from oracle_py import qp_solve
     cfg = load_config()
     B = 8
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, initial_run=False)
     for it in range(3):
         g.get_real_time_update(states, 0.0, ees)
         st, err = g.status(); sz = g.sizes(); xr = g.raw_qp_minimiser()
@@ -206,12 +164,8 @@ def test_full_batch_minimisers_on_identical_qps():
     from oracle_py import qp_solve
     cfg = load_config()
     B = 256
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees)
     g.get_real_time_update(states, 0.0, ees)
     st, err = g.status(); sz = g.sizes(); xr = g.raw_qp_minimiser()
     assert np.all(err == 0)
@@ -244,11 +198,9 @@ def test_device_resident_protocol_equals_host_driven_loop():
     cfg = load_config()
     s0 = np.array(cfg['srb_init'], float)
     B = 3
-    ga = host.BatchMPC(cfg, B); ga.set_state_trajectory_warm_start(s0); ga.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    gb = host.BatchMPC(cfg, B); gb.set_state_trajectory_warm_start(s0); gb.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    ga.enable_fast_termination(); gb.enable_fast_termination()      # the fused launch of ga then makes the lower-start attempts, gb's one-step launches do not
-    ga.create_initial_run(s0, EE0); gb.create_initial_run(s0, EE0)
-    o = OracleMPC(cfg); o.set_warmstart(s0); o.initial_run(s0, EE0)
+    # bench.py's step_rule_mode: the fused launch of ga then makes the lower-start attempts, gb's one-step launches do not
+    ga, gb = (host.BatchMPC.cold_start(cfg, [s0] * B, EE_NOMINAL, mode=(host.FAST_TOL_STEP, host.FAST_START_MU)) for _ in range(2))
+    o = OracleMPC(cfg); o.set_warmstart(s0); o.initial_run(s0, EE_NOMINAL)
     K = 7
     ga.rti_advance(0, K); ga.synchronize()
     dt = cfg['integrator_dt']
@@ -271,15 +223,11 @@ def test_fused_kernel_equals_one_launch_per_phase():
     one launch per phase: bit-identical trajectories, knot tables and QP solutions"""
     cfg = load_config()
     B = 8
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
+    states, ees = instances(cfg, config_b_instance, B)
     res = []
     for fused in (True, False):
-        g = host.BatchMPC(cfg, B)
-        g.set_state_trajectory_warm_start(states)
-        g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-        g.set_solver_step_rule(host.FAST_TOL_STEP, 0.0)           # step rule on, no lower-start attempt (it belongs to the K-step launch alone: off on both sides)
-        g.create_initial_run(states, ees)
+        # step rule on, no lower-start attempt (it belongs to the K-step launch alone: off on both sides)
+        g = host.BatchMPC.cold_start(cfg, states, ees, mode=(host.FAST_TOL_STEP, 0.0))
         (g.rti_advance if fused else g.rti_advance_unfused)(0, 7)
         g.synchronize()
         st, err = g.status()
@@ -293,7 +241,7 @@ def test_updated_contact_times_parity():
     """MPC::UpdateContactTimes (mpc.cpp:1085-1088 -> EndEffectorSplines::SetContactTimes :860-892) then an RTI step."""
     cfg = load_config()
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
     ct = [o.contact_times(e)[0] for e in range(4)]
     new = [c.copy() for c in ct]
     new[0][1] += 0.03; new[0][2] += 0.01; new[3][2] -= 0.02; new[1][1] += 0.015
@@ -303,8 +251,8 @@ def test_updated_contact_times_parity():
         arr[:, e, :len(new[e])] = new[e]
     g.update_contact_times(arr)
     check_knots(g, o)
-    g.get_real_time_update(s0, 0.0, EE0)
-    so = o.rti(s0, 0.0, EE0)
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL)
+    so = o.rti(s0, 0.0, EE_NOMINAL)
     st, err = g.status()
     assert err[0] == 0 and status_class(st[0]) == status_class(so)
     n = o.sizes()['n']
@@ -318,7 +266,7 @@ def test_early_touchdown_adjustment_parity():
     knot (and the stance-interior knots) re-timed; knot tables bit-exact, the following RTI step within tolerance"""
     cfg = load_config()
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
     dt = cfg['integrator_dt']
     changed = False
     for i in range(8):
@@ -348,7 +296,7 @@ def test_statistics_log_line_format(tmp_path):
     """MPC::PrintStatLineToFile (mpc.cpp:901-989): 10 right-aligned columns of width 15, values of the last solve"""
     cfg = load_config()
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
     state = o.states()[1]
     ee = np.array([[o.ee_value(e, 1, c, 0.0) for c in range(3)] for e in range(4)])
     o.rti(state, 0.0, ee); g.get_real_time_update(state, 0.0, ee)     # a step with a real Armijo decision
@@ -371,8 +319,8 @@ def test_statistics_log_line_format(tmp_path):
 def test_short_horizon_config_a():
     cfg = load_config(num_nodes=10)       # Config A of BASELINE.json: N=10 plumbing case
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0); o.initial_run(s0, EE0)
-    g.get_real_time_update(s0, 0.0, EE0); so = o.rti(s0, 0.0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL); so = o.rti(s0, 0.0, EE_NOMINAL)
     sz = g.sizes()[0]
     assert (sz[0], sz[1]) == (o.sizes()['n'], o.sizes()['m']) == (252, 732)
     assert status_class(g.status()[0][0]) == status_class(so)
@@ -384,12 +332,8 @@ def test_full_batch_properties():
     a result does not depend on the instance's slot in the batch, dynamics rows of the QP hold for the QP minimiser."""
     cfg = load_config()
     B = 256
-    states, ees = zip(*[config_b_instance(cfg, b % 16) for b in range(B)])      # 16 distinct problems, 16 copies each
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_b_instance, [b % 16 for b in range(B)])      # 16 distinct problems, 16 copies each
+    g = host.BatchMPC.cold_start(cfg, states, ees)
     g.rti_advance(0, 3); g.synchronize()
     x = g.qp_solution(); st, err = g.status(); sz = g.sizes()
     assert np.all(err == 0) and all(status_class(v) == 'ok' for v in st)
@@ -421,13 +365,8 @@ def test_config_b_all_instances_against_oracle_fixture():
     X = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'config_b_rti_x.npz'))['x']      # full minimisers [256][steps][412]
     cfg = load_config()
     B = 256
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.set_solver_step_rule(0.0, 0.0)              # own-path comparison against a fixture of the reference criterion: both sides by that criterion
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=(0.0, 0.0))   # own-path comparison against a fixture of the reference criterion: both sides by that criterion
     cls = lambda v: 'solved' if v <= 1 else ('infeasible' if v in (3, 5) else 'unconverged')
     alive = np.ones(B, bool)
     n_inf = 0
@@ -471,7 +410,7 @@ def test_capacity_overflow_fails_loudly():
     """More spline variables than the kernel's LDS budget (160) must raise an error bit, never a silent wrong answer."""
     cfg = load_config()
     g, o, s0 = make_pair(cfg)
-    g.create_initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL)
     # squeeze many short phases into the horizon: contact times 0.2 apart are legal for the reference (gait_optimizer.cpp:412)
     kg = g.knots(0)
     nct = [int(np.sum(kg['kinds'][e, :kg['nk'][e]] <= 1)) for e in range(4)]
@@ -479,7 +418,7 @@ def test_capacity_overflow_fails_loudly():
     for e in range(4):
         arr[:, e, :nct[e]] = 0.05 * np.arange(nct[e])      # 50 ms phases -> horizon needs > 160 variables
     g.update_contact_times(arr)
-    g.get_real_time_update(s0, 0.0, EE0)
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL)
     st, err = g.status()
     assert (err[0] & 16) != 0 and st[0] == 8
 
@@ -489,14 +428,11 @@ def test_infeasible_qps_of_the_pushed_configuration_are_infeasible_for_the_oracl
     PrimalInfeasible in the bench's timed region (`all_solved: false` there).  On the SAME exported QPs the oracle's solver gives the same
     status -- they are properties of the pushed workload, not failures of the device solver."""
     from oracle_py import qp_solve
-    from srbm_loader.workloads import config_d_instance
     cfg = load_config('a1_config_distr_rejection')
     N = cfg['num_nodes']; nx = 12 * (N + 1)
     ids = [150, 441, 3]
-    states, ees = zip(*[config_d_instance(cfg, b) for b in ids])
-    states, ees = np.array(states), np.array(ees).reshape(len(ids), 12)
-    g = host.BatchMPC(cfg, len(ids)); g.set_state_trajectory_warm_start(states)
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_d_instance, ids)
+    g = host.BatchMPC.cold_start(cfg, states, ees)
     seen = {0: 0, 3: 0}
     for i in range(15):
         g.rti_advance(i, 1); g.synchronize()

@@ -14,9 +14,9 @@ import pytest
 
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
+from srbm_loader.workloads import EE_NOMINAL
 
 pytestmark = pytest.mark.gpu
-EE0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]], float)
 DERIV_MARGIN = 1e-4            # test/mpc_test.cpp:122
 
 
@@ -24,15 +24,12 @@ DERIV_MARGIN = 1e-4            # test/mpc_test.cpp:122
 def test_contact_time_partials_against_finite_differences_and_the_oracle(cfgname):
     cfg = load_config(cfgname)
     s0 = np.array(cfg['srb_init'], float)
-    o = OracleMPC(cfg); o.set_warmstart(s0); o.initial_run(s0, EE0)
+    o = OracleMPC(cfg); o.set_warmstart(s0); o.initial_run(s0, EE_NOMINAL)
     ct = [o.contact_times(e)[0] for e in range(4)]
     pairs = [(ee, idx) for ee in range(4) for idx in range(1, len(ct[ee]))]       # mpc_test.cpp:130-131: idx starts at 1
     assert len(pairs) >= 12
     B = 1 + len(pairs)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(s0)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.create_initial_run(s0, EE0)
+    g = host.BatchMPC.cold_start(cfg, [s0] * B, EE_NOMINAL)
     # the device's schedule is the oracle's, bit for bit
     tr = g.get_trajectory(0, 1)[0]
     for e in range(4):
@@ -46,7 +43,7 @@ def test_contact_time_partials_against_finite_differences_and_the_oracle(cfgname
     # (2) entry-wise against the oracle: its partials need the QP data of a solve (`mpc.GetRealTimeUpdate`, :122), the trajectory is `traj`.
     #     Each side evaluates on ITS trajectory of the initial run (ten SQP solves each: node values agree to ~1e-7 relative, the partials
     #     differentiate cubic segments of 0.1 s), hence 1e-5 of the largest entry of each output rather than round-off; the sparsity patterns coincide
-    assert o.rti(s0, 0.0, EE0) == 0
+    assert o.rti(s0, 0.0, EE_NOMINAL) == 0
     worst = 0.0
     for (ee, idx) in pairs:
         dA, dG, db, dh = analytic[(ee, idx)]
@@ -68,7 +65,7 @@ def test_contact_time_partials_against_finite_differences_and_the_oracle(cfgname
     for k, (ee, idx) in enumerate(pairs):
         times[1 + k, ee, idx] += dt
     g.update_contact_times(times)                      # mpc2.UpdateContactTimes(mod_times), :132
-    g.get_real_time_update(s0, 0.0, EE0)               # :133
+    g.get_real_time_update(s0, 0.0, EE_NOMINAL)               # :133
     sz = g.sizes()
     assert (sz == sz[0]).all()                         # REQUIRE(num_force_box == ...), REQUIRE(num_cone == ...): sizes do not move
     n, ns = int(sz[0, 0]), int(sz[0, 7])
@@ -93,11 +90,10 @@ def test_contact_time_partials_against_finite_differences_and_the_oracle(cfgname
 def test_partials_entry_rejects_what_does_not_exist():
     cfg = load_config('a1_configuration')
     s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC(cfg, 1)
-    g.set_state_trajectory_warm_start(s0)
+    g = host.BatchMPC.cold_start(cfg, s0, None, initial_run=False)
     with pytest.raises(RuntimeError):
         g.param_partials(0, 0, 1)                      # no QP solved yet
-    g.create_initial_run(s0, EE0)
+    g.create_initial_run(s0, EE_NOMINAL)
     with pytest.raises(RuntimeError):
         g.param_partials(0, 0, 31)                     # contact index beyond the schedule
     with pytest.raises(RuntimeError):

@@ -21,10 +21,8 @@ sys.path.insert(0, %(root)r)
 from srbm_loader import host, workloads
 cfg = host.load_config('a1_config_distr_rejection')
 B = int(sys.argv[1]); steps = int(sys.argv[2]); closed = int(sys.argv[3]); rewind = int(sys.argv[4])
-st, ee = zip(*[workloads.config_d_instance(cfg, b %% 512) for b in range(B)])
-st, ee = np.array(st), np.array(ee).reshape(B, 12)
-g = host.BatchMPC(cfg, B); g.set_state_trajectory_warm_start(st); g.set_solver_step_rule(float(os.environ.get('QUEUE_TEST_TOL_STEP', '0')), 0.1)
-g.create_initial_run(st, ee)
+st, ee = workloads.instances(cfg, workloads.config_d_instance, [b %% 512 for b in range(B)])
+g = host.BatchMPC.cold_start(cfg, st, ee, mode=(float(os.environ.get('QUEUE_TEST_TOL_STEP', '0')), 0.1))
 if closed:
     g.plant_set_state(st)
     imp = np.zeros((B, 6)); imp[::7, 0] = 0.4; imp[::11, 1] = -0.3

@@ -17,10 +17,10 @@ import io
 import numpy as np
 import pytest
 
+from gpu_kit import advance, assert_bitwise, same_bytes, snapshot
 from oracle_py import load_config
 from srbm_loader import host
-from srbm_loader.workloads import config_b_instance
-from test_gpu_launch_equivalence import advance, assert_bitwise, snapshot
+from srbm_loader.workloads import config_b_instance, instances
 
 pytestmark = pytest.mark.gpu
 MODE = (0.0, 0.1)           # lower-start attempts: solve flags other than 0 in the open-loop protocol
@@ -37,13 +37,8 @@ def step(g, closed, first, steps):
 
 def cold_start(cfg, B, large=None):
     """a batch after its cold start, with a plant and pushes at 2.5 dt on instances 0 and 1 (the open-loop protocol does not look at them)"""
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B, large=large)
-    g.set_state_trajectory_warm_start(states)
-    g.set_solver_tolerances(1e-15, 1e-15, 1e-10, 200)
-    g.set_solver_step_rule(*MODE)
-    g.create_initial_run(states, ees)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE, large=large)
     g.plant_set_state(states)
     imp = np.zeros((B, 6)); imp[0, 0] = 0.4; imp[1, 1] = -0.3
     push_time = np.full(B, 1e9); push_time[:2] = 2.5 * cfg['integrator_dt']
@@ -109,13 +104,6 @@ def run_split(base, closed, split, log=True):
     out = dict(records=g.step_log() if log else None, final=snapshot(g, closed), infos=infos)
     g.close()
     return out
-
-
-def same_bytes(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if a.tobytes() != b.tobytes():
-        bad = np.argwhere(a.view(np.uint64) != b.view(np.uint64))
-        raise AssertionError('%s: differs at (step, instance, field) %s' % (what, bad[:8].tolist()))
 
 
 @pytest.fixture(scope='module')

@@ -7,8 +7,10 @@ import sys
 import numpy as np
 import pytest
 
-from oracle_py import load_config, qp_solve
+from gpu_kit import wbc_inputs
+from oracle_py import qp_solve
 from srbm_loader import host
+from srbm_loader.workloads import config_b_instance, instances
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'oracle'))
@@ -19,24 +21,9 @@ pytestmark = pytest.mark.gpu
 CONTACTS = [[1, 1, 1, 1], [1, 0, 0, 1], [0, 1, 1, 0], [1, 1, 1, 0], [0, 0, 1, 0], [0, 0, 0, 0]]
 
 
-def make(B, seed=3):
-    cfg = load_config()
-    rng = np.random.default_rng(seed)
-    q0 = np.array(cfg['init_config'], float)
-    q = np.tile(q0, (B, 1))
-    q[:, :3] += rng.normal(size=(B, 3)) * 0.03
-    quat = q[:, 3:7] + np.concatenate([rng.normal(size=(B, 3)) * 0.05, np.zeros((B, 1))], axis=1)
-    q[:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True)
-    q[:, 7:] += rng.normal(size=(B, 12)) * 0.1
-    v = rng.normal(size=(B, 18)) * 0.1
-    q_des = np.tile(q0, (B, 1)); q_des[:, 7:] += rng.normal(size=(B, 12)) * 0.02
-    v_des = rng.normal(size=(B, 18)) * 0.05
-    return cfg, q, v, q_des, v_des, rng
-
-
 def test_assembled_qp_and_solution_match_the_oracle():
     B = len(CONTACTS) * 2
-    cfg, q, v, q_des, v_des, rng = make(B)
+    cfg, q, v, q_des, v_des, rng = wbc_inputs(B)
     contact = np.array([CONTACTS[b % len(CONTACTS)] for b in range(B)], np.int32)
     fdes = np.zeros((B, 12))
     for b in range(B):
@@ -69,7 +56,7 @@ def test_full_batch_controller_properties():
     """256 instances: every QP solves; the solution satisfies the floating-base dynamics, the torque limits, the friction pyramid and the
     force bounds; standing still at the nominal configuration with the weight as the force target needs torques that hold the weight"""
     B = 256
-    cfg, q, v, q_des, v_des, rng = make(B, seed=9)
+    cfg, q, v, q_des, v_des, rng = wbc_inputs(B, seed=9)
     contact = np.array([CONTACTS[b % 3] for b in range(B)], np.int32)
     fdes = np.zeros((B, 12))
     for b in range(B):
@@ -117,13 +104,9 @@ def test_device_pointer_entries_of_the_control_tick_equal_the_host_pointer_entri
         def __del__(self):
             hip.hipFree(self.p)
     B = 32
-    cfg, q, v, q_des, v_des, rng = make(B, seed=21)
-    from srbm_loader.workloads import config_b_instance
-    states, ees = zip(*[config_b_instance(cfg, b) for b in range(B)])
-    states, ees = np.array(states), np.array(ees).reshape(B, 12)
-    g = host.BatchMPC(cfg, B)
-    g.set_state_trajectory_warm_start(states)
-    g.create_initial_run(states, ees)
+    cfg, q, v, q_des, v_des, rng = wbc_inputs(B, seed=21)
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees)
     t0 = g.get_trajectory(0, 1)[0].init_time + 2e-3
     q0 = np.tile(np.array(cfg['init_config'], float), (B, 1))
     qh, vh, fh, sth = g.get_targets_from_traj(t0, q0)
@@ -156,7 +139,7 @@ def test_a_clone_carries_the_whole_body_model_and_close_releases_borrowers_first
     has not been set"); BatchMPC.close() releases the gait optimisers that borrow the batch before the batch (round 2: the library refused the
     destroy, the binding dropped its handle and the device batch leaked)"""
     B = 4
-    cfg, q, v, q_des, v_des, rng = make(B, seed=5)
+    cfg, q, v, q_des, v_des, rng = wbc_inputs(B, seed=5)
     contact = np.ones((B, 4), np.int32)
     fdes = np.tile([0, 0, cfg['mass'] * 9.81 / 4], (B, 4))
     g = host.BatchMPC(cfg, B)
@@ -176,7 +159,7 @@ def test_a_row_structure_the_assembly_does_not_cover_is_reported():
     contact).  A zero torque bound turns a torque row into an equality and breaks that order: the kernel reports it (status 8, zero control action --
     the path of "Could not solve WBC QP. Returning 0 control action.", qp_control.cpp:88-92) instead of assembling the wrong matrix"""
     B = 4
-    cfg, q, v, q_des, v_des, rng = make(B, seed=11)
+    cfg, q, v, q_des, v_des, rng = wbc_inputs(B, seed=11)
     cfg = dict(cfg); cfg['torque_bounds'] = list(cfg['torque_bounds']); cfg['torque_bounds'][3] = 0.0
     contact = np.ones((B, 4), np.int32)
     fdes = np.tile([0, 0, cfg['mass'] * 9.81 / 4], (B, 4))

@@ -6,11 +6,8 @@ import math
 import numpy as np
 import pytest
 
+from gpu_kit import EE_TEST         # foot positions used by the reference's test: test/mpc_test.cpp:97-101
 from oracle_py import OracleMPC, load_config
-
-# foot positions used by the reference's test: test/mpc_test.cpp:97-101
-EE_TEST = np.array([[0.1526, 0.12523, 0.011089], [0.1526, -0.12523, 0.011089],
-                    [-0.208321844, 0.1363286, 0.01444], [-0.208321844, -0.1363286, 0.01444]])
 
 
 def make(cfg_name='a1_configuration', **over):
