@@ -190,6 +190,15 @@ static int use_batch(srbm_batch* h) {
 }
 // the IPM variant of every launch path: the _long kernels beyond K3_SHORT_N nodes (srbm_k3_ipm.hiph)
 static bool k3_long(const srbm_batch* h) { return h->hp.N > K3_SHORT_N; }
+// The eight multi-step kernels (srbm_fused.hiph) by [step queues][_long][_logged]: alloc_batch raises the dynamic-LDS limit of each, launch_fused
+// launches one.  Their argument lists share the first nine; the queued ones go on with (queues, batch), the logged ones end with the log arguments.
+static const void* multi_step_kernel(bool queued, bool long_n, bool logged) {
+#define K(name) reinterpret_cast<const void*>(name)
+    static const void* const table[2][2][2] = {{{K(srbm_rti_fused), K(srbm_rti_fused_logged)}, {K(srbm_rti_fused_long), K(srbm_rti_fused_long_logged)}},
+                                               {{K(srbm_rti_queued), K(srbm_rti_queued_logged)}, {K(srbm_rti_queued_long), K(srbm_rti_queued_long_logged)}}};
+#undef K
+    return table[queued][long_n][logged];
+}
 // ---- step log (srbm_steplog.hiph): the entries that log ask for room BEFORE they queue anything, so that a refused call leaves the batch untouched ----
 static int log_room(const srbm_batch* h, const char* fn, int steps) {
     if (!h->d_log || steps <= h->log_cap - h->log_used) return 0;
@@ -388,17 +397,11 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     const struct { const void* kernel; size_t lds; } dyn_lds[] = {
         {reinterpret_cast<const void*>(srbm_k3_ipm), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_k3_ipm_long), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_fused), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_fused_long), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_queued), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_queued_long), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_fused_logged), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_fused_long_logged), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_queued_logged), K3_LDS_LAUNCH_BYTES},
-        {reinterpret_cast<const void*>(srbm_rti_queued_long_logged), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_k3_normal_matrix), K3_LDS_LAUNCH_BYTES},
         {reinterpret_cast<const void*>(srbm_k_gait_sensitivity), KG_DYN_LDS_BYTES}};
     for (const auto& k : dyn_lds) HIPCHK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+    for (int i = 0; i < 8; i++)
+        HIPCHK(hipFuncSetAttribute(multi_step_kernel(i & 4, i & 2, i & 1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K3_LDS_LAUNCH_BYTES));
     HIPCHK(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
     { const char* e = std::getenv("SRBM_NO_STEP_QUEUE"); h->queued_ok = !(e && e[0] == '1'); }
     h->params_dirty = true;
@@ -674,24 +677,15 @@ static int launch_fused(srbm_batch* h, const char* fn, int first_index, int step
     if (queued) {
         if (!h->queues) HIPCHK(hipMalloc(&h->queues, sizeof(SrbmQueue) * SRBM_NQUEUES));
         hipLaunchKernelGGL(srbm_k_queue_init, dim3(SRBM_NQUEUES), dim3(256), 0, h->stream, h->queues, h->batch);
-        if (logged) {
-            const auto kernel = long_n ? srbm_rti_queued_long_logged : srbm_rti_queued_logged;
-            hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch, log_args(h));
-        } else {
-            const auto kernel = long_n ? srbm_rti_queued_long : srbm_rti_queued;
-            hipLaunchKernelGGL(kernel, dim3(h->n_cu), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                               h->d_state, h->d_time, h->d_ee, pl, h->queues, h->batch);
-        }
-    } else if (logged) {
-        const auto kernel = long_n ? srbm_rti_fused_long_logged : srbm_rti_fused_logged;
-        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                           h->d_state, h->d_time, h->d_ee, pl, log_args(h));
-    } else {
-        const auto kernel = long_n ? srbm_rti_fused_long : srbm_rti_fused;
-        hipLaunchKernelGGL(kernel, dim3(h->batch), dim3(K3_THREADS), K3_LDS_LAUNCH_BYTES, h->stream, h->dp, h->insts, h->works, first_index, steps,
-                           h->d_state, h->d_time, h->d_ee, pl);
     }
+    // one workgroup per instance, or (step queues) a resident grid of one workgroup per CU; the argument list of the kernel chosen (multi_step_kernel)
+    SrbmStepLogArgs lg = log_args(h);
+    void* args[12] = {&h->dp, &h->insts, &h->works, &first_index, &steps, &h->d_state, &h->d_time, &h->d_ee, &pl};
+    int na = 9;
+    if (queued) { args[na++] = &h->queues; args[na++] = &h->batch; }
+    if (logged) args[na++] = &lg;
+    (void)hipLaunchKernel(multi_step_kernel(queued, long_n, logged), dim3(queued ? h->n_cu : h->batch), dim3(K3_THREADS), args, K3_LDS_LAUNCH_BYTES,
+                          h->stream);          // (its error, if any, is the one hipGetLastError reports below)
     if (logged) h->log_used += steps;
     if (tm) { HIPCHK(hipEventRecord(h->ev_stop[h->ev_used], h->stream)); h->ev_steps[h->ev_used] = steps; h->ev_used++; }
     HIPCHK(hipGetLastError());

@@ -147,7 +147,7 @@ typedef struct SrbmWork {
     double H[SRBM_HPACK];                         /* reduced Hessian, packed lower, row-major */
     double g[SRBM_NUMAX];
     double Sig[SRBM_NEEROW][SRBM_NUMAX];          /* rows c of S_k, k=4..N, c in {x,y}: row index 2*(k-4)+c; COMPACT: entry q = force variable q of coordinate c over the four feet
-                                                     (the only non-zeros of the row; srbm_k3_ipm.hiph, K3Smem) */
+                                                     (the only non-zeros of the row; srbm_k3_lds.hiph, K3Smem) */
     double sig0[SRBM_NEEROW];                     /* affine part s_k[c] */
     /* ---- IPM (kernel 3) ---- */
     double u[SRBM_NUMAX];                         /* QP minimiser, spline variables (full vector incl. pinned) */

@@ -282,7 +282,7 @@ FEET0 = np.array([[0.2, 0.2, 0], [0.2, -0.2, 0], [-0.2, 0.2, 0], [-0.2, -0.2, 0]
 
 def first_rti_sizes(cfg, phase=None):
     """(n_u, wc, n_ineq) of the first RTI step from srb_init with the feet at FEET0: n_u = n - 12 (N + 1) spline variables, wc = n_force / 3 (the
-    width of the compact dense rows, srbm_k3_ipm.hiph), the inequality rows.  phase: after the cold start the contact times are set that far
+    width of the compact dense rows, srbm_k3_lds.hiph), the inequality rows.  phase: after the cold start the contact times are set that far
     apart, as many per foot as the cold start has"""
     N = cfg['num_nodes']
     s0 = np.array(cfg['srb_init'], float)

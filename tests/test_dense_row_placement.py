@@ -1,4 +1,4 @@
-"""Where the IPM puts the compact dense state rows (csrc/srbm_k3_ipm.hiph: k3_sig_placement, the arithmetic k3_make_smem decides with): in LDS --
+"""Where the IPM puts the compact dense state rows (csrc/srbm_k3_lds.hiph: k3_sig_placement, the arithmetic k3_make_smem decides with): in LDS --
 the tail of the packed-matrix window and the space behind the LDS map -- or, when they do not fit, read from W.Sig in L2 in every pass.  Both
 libraries answer through srbm_debug_dense_row_placement on a machine without a GPU.  The sizes of each case come from the CPU oracle (n_u = n -
 12 (N + 1), wc = n_force / 3), so the pins hold the schedules the end-to-end tests run (tests/test_gpu_dense_rows.py) to the branch they exist

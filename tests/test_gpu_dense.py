@@ -1,4 +1,4 @@
-"""GPU unit tests of the dense fp64 building blocks of the IPM kernel (bilevel-gait-gen_amd/csrc/srbm_dense.hiph, srbm_k3_ipm.hiph) against
+"""GPU unit tests of the dense fp64 building blocks of the IPM kernel (bilevel-gait-gen_amd/csrc/srbm_dense.hiph, srbm_k3_normal.hiph, srbm_k3_rows.hiph) against
 numpy, in both builds: the standard one (packed matrix in LDS, n <= 160) and the LARGE one (packed matrix in global memory, n <= 240,
 DN_MAXT = DN_SLOTS = 15), through the hooks of csrc/srbm_dense_hooks.hiph.
 

@@ -1,5 +1,5 @@
 """End-to-end parity on the IPM paths the other GPU tests do not reach: the compact dense state rows read from L2 instead of LDS (sig_lds = 0 in
-csrc/srbm_k3_ipm.hiph: eval_rows_prep, the un-fused branch of gt_apply, the W.Sig reads of the sparse assembly), horizons beyond N = 40 in the
+csrc/srbm_k3_rows.hiph: eval_rows_prep, the un-fused branch of gt_apply; srbm_k3_normal.hiph: the W.Sig reads of the sparse assembly), horizons beyond N = 40 in the
 LARGE build (N = 100: more than 2048 inequality rows, the fifth of the K3_RPT register slots per thread live), and the LARGE build's capacity
 guard.  Each case first asserts that it takes the branch it exists for: the placement of its dense rows through srbm_debug_dense_row_placement
 (the function k3_make_smem decides with; tests/test_dense_row_placement.py pins it on the CPU), n_u and wc = n_force / 3 from the oracle's sizes.
