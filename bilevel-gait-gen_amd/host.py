@@ -42,7 +42,7 @@ class Model(C.Structure):            # srbm_model
     _fields_ = [('mass', C.c_double), ('Ir', C.c_double * 9), ('hip_xy', C.c_double * 8)]
 
 
-KMAX, NODES_MAX = 32, 101
+KMAX, NODES_MAX, RCCL_UNIQUE_ID_BYTES = 32, 101, 128       # SRBM_TRAJ_KMAX, SRBM_TRAJ_NODES_MAX, SRBM_RCCL_UNIQUE_ID_BYTES = sizeof(ncclUniqueId)
 # srbm_set_solver_step_rule: a new batch runs every solve to the reference's gap criterion (0, 0); these are the values bench.py opts into for
 # its headline line (include/srbm_rti.h: SRBM_FAST_TOL_STEP, SRBM_FAST_START_MU)
 FAST_TOL_STEP, FAST_START_MU = 1e-5, 0.1
@@ -69,7 +69,7 @@ class Trajectory(C.Structure):       # srbm_trajectory: mpc::Trajectory as a fla
 
     def _eval(self, ee, time):
         f = (C.c_double * 3)(); p = (C.c_double * 3)(); c = C.c_int(0)
-        rc = lib().srbm_trajectory_eval(C.byref(self), int(ee), C.c_double(time), f, p, C.byref(c))
+        rc = lib().srbm_trajectory_eval(C.byref(self), int(ee), time, f, p, C.byref(c))
         if rc != 0:
             raise RuntimeError('trajectory lookup failed at t=%g (error bits %d)' % (time, rc))   # the reference throws std::runtime_error
         return np.array(f[:]), np.array(p[:]), bool(c.value)
@@ -88,6 +88,160 @@ class Trajectory(C.Structure):       # srbm_trajectory: mpc::Trajectory as a fla
         for ee in range(4):
             out.append([self.knot_time[ee][k] for k in range(self.nk[ee]) if self.knot_kind[ee][k] <= 1])
         return out
+
+
+# ---- the prototype of every exported function, and the one place that types the binding ----
+# C type -> ctypes type, `const` left out.  A host array is a typed pointer: a pointer to another element type or a bare integer is refused before
+# the call.  Handles, void* and DEVICE pointers (`dev*`: the *_dev parameters of the header, whatever they point to) are c_void_p: integer addresses.
+C_TYPES = {
+    'void': None, 'int': C.c_int, 'double': C.c_double, 'long': C.c_long, 'char*': C.c_char_p, 'char**': C.POINTER(C.c_char_p),
+    'double*': _dp, 'int*': _ip, 'long long*': C.POINTER(C.c_longlong),
+    'srbm_batch*': C.c_void_p, 'srbm_gait*': C.c_void_p, 'ncclComm_t': C.c_void_p, 'void*': C.c_void_p, 'dev*': C.c_void_p,
+    'srbm_batch**': C.POINTER(C.c_void_p), 'srbm_gait**': C.POINTER(C.c_void_p), 'ncclComm_t*': C.POINTER(C.c_void_p),
+    'srbm_mpc_info*': C.POINTER(MPCInfo), 'srbm_model*': C.POINTER(Model), 'srbm_wbc_model*': C.POINTER(WbcModel), 'srbm_trajectory*': C.POINTER(Trajectory),
+    'srbm_leg_kinematics*': _dp,         # no mirror: its one member double origin[4][4][3] is passed as a flat array
+}
+
+
+def prototypes(text, types=C_TYPES):
+    """name -> (restype, argtypes) from lines `ret name(type, type, ...)` spelled with the keys of `types`"""
+    table = {}
+    for line in text.strip().split('\n'):
+        head, args = line.strip().rstrip(')').split('(')
+        ret, name = head.rsplit(None, 1)
+        table[name] = (types[ret], tuple(types[a.strip()] for a in args.split(',') if a.strip()))
+    return table
+
+
+def declare(L, table):
+    """set restype and argtypes of every function of `table` on the loaded library L; the only place that sets either"""
+    for name, (restype, argtypes) in table.items():
+        f = getattr(L, name)                # AttributeError ('undefined symbol') if the library lacks it
+        f.restype, f.argtypes = restype, argtypes
+    return L
+
+
+# include/srbm_rti.h, then the srbm_debug_* hooks that only csrc/srbm_capi.hip declares (tests/test_abi_prototypes.py holds both to the C text and to
+# the symbols of the two libraries)
+PROTOTYPES = prototypes('''\
+int srbm_batch_create(srbm_batch**, int, srbm_mpc_info*, srbm_model*, int)
+int srbm_batch_create_each(srbm_batch**, int, srbm_mpc_info*, srbm_model*, int)
+int srbm_get_instance_model(srbm_batch*, int, srbm_mpc_info*, srbm_model*)
+int srbm_batch_destroy(srbm_batch*)
+char* srbm_last_error()
+int srbm_batch_clone(srbm_batch*, srbm_batch**)
+int srbm_batch_size(srbm_batch*)
+int srbm_get_capacity(int*)
+int srbm_num_nodes(srbm_batch*)
+int srbm_add_quadratic_tracking_cost(srbm_batch*, double*, double*)
+int srbm_set_quadratic_final_cost(srbm_batch*, double*)
+int srbm_set_linear_final_cost(srbm_batch*, double*)
+int srbm_add_force_cost(srbm_batch*, double)
+int srbm_add_quadratic_tracking_cost_each(srbm_batch*, int, int, double*, double*)
+int srbm_set_quadratic_final_cost_each(srbm_batch*, int, int, double*)
+int srbm_set_linear_final_cost_each(srbm_batch*, int, int, double*)
+int srbm_add_force_cost_each(srbm_batch*, int, int, double*)
+int srbm_set_state_trajectory_warm_start(srbm_batch*, double*)
+int srbm_set_solver_tolerances(srbm_batch*, double, double, double, int)
+int srbm_set_solver_step_rule(srbm_batch*, double, double)
+int srbm_get_solver_step_rule(srbm_batch*, double*, double*)
+int srbm_get_solve_flags(srbm_batch*, int*)
+int srbm_create_initial_run(srbm_batch*, double*, double*)
+int srbm_get_real_time_update(srbm_batch*, double*, double*, double*)
+int srbm_get_real_time_update_dev(srbm_batch*, dev*, dev*, dev*)
+int srbm_rti_advance(srbm_batch*, int, int)
+int srbm_rti_advance_unfused(srbm_batch*, int, int)
+int srbm_plant_set_state(srbm_batch*, double*)
+int srbm_plant_get_state(srbm_batch*, double*)
+int srbm_plant_set_push(srbm_batch*, double*, double*)
+int srbm_closed_loop_advance(srbm_batch*, int, int, int, int)
+int srbm_synchronize(srbm_batch*)
+void* srbm_stream(srbm_batch*)
+int srbm_step_log_record_doubles()
+int srbm_step_log_enable(srbm_batch*, int)
+int srbm_step_log_reset(srbm_batch*)
+int srbm_step_log_count(srbm_batch*, int*)
+int srbm_step_log_get(srbm_batch*, int, int, double*)
+int srbm_step_log_copy_dev(srbm_batch*, int, int, dev*)
+int srbm_sizeof_trajectory()
+int srbm_get_trajectory(srbm_batch*, int, int, srbm_trajectory*)
+int srbm_set_warm_start_trajectory(srbm_batch*, int, int, srbm_trajectory*)
+int srbm_trajectory_eval(srbm_trajectory*, int, double, double*, double*, int*)
+int srbm_trajectory_splines_as_vec(srbm_trajectory*, double*, int, int*, int*)
+int srbm_convert_manifold_to_tangent(double*, double*)
+int srbm_convert_tangent_to_manifold(double*, double*)
+int srbm_eval_trajectory(srbm_batch*, double*, double*, double*, int*)
+int srbm_eval_trajectory_dev(srbm_batch*, dev*, dev*, dev*, dev*)
+int srbm_get_ee_box_center(srbm_batch*, double*)
+int srbm_get_cost(srbm_batch*, double*)
+int srbm_get_avg_cost(srbm_batch*, double*)
+int srbm_get_merit(srbm_batch*, double*, double*)
+int srbm_update_contact_times(srbm_batch*, double*, int)
+int srbm_adjust_for_current_contacts(srbm_batch*, double*, int*)
+int srbm_gait_create(srbm_batch*, srbm_gait**)
+int srbm_gait_destroy(srbm_gait*)
+int srbm_gait_set_contact_times_from_trajectory(srbm_gait*)
+int srbm_gait_get_contact_times(srbm_gait*, double*, int*)
+int srbm_gait_compute_sensitivity(srbm_gait*)
+int srbm_gait_get_sensitivity(srbm_gait*, double*, int)
+int srbm_gait_compute_gradient(srbm_gait*)
+int srbm_gait_get_gradient(srbm_gait*, double*, int*)
+int srbm_gait_get_param_partials(srbm_batch*, int, int, int, double*, double*, double*, double*)
+int srbm_gait_optimize_contact_times(srbm_gait*, double*)
+int srbm_gait_get_lp_result(srbm_gait*, int*, double*)
+int srbm_gait_set_step(srbm_gait*, double*)
+int srbm_gait_get_step(srbm_gait*, double*)
+int srbm_gait_line_search(srbm_gait*, double*, double*, double*, int*, double*)
+int srbm_gait_rti_advance(srbm_gait*, int, int, int)
+int srbm_gait_get_candidate_status(srbm_gait*, int*, int*)
+srbm_batch* srbm_gait_debug_candidates(srbm_gait*)
+int srbm_set_leg_kinematics(srbm_batch*, srbm_leg_kinematics*)
+int srbm_forward_kinematics(srbm_batch*, double*, double*)
+int srbm_inverse_kinematics(srbm_batch*, double*, double*, double*, double*, int*, int*)
+int srbm_get_targets_from_traj(srbm_batch*, double*, double*, double*, double*, int*)
+int srbm_get_targets_from_traj_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*)
+int srbm_set_wbc_model(srbm_batch*, srbm_wbc_model*)
+int srbm_qp_control(srbm_batch*, double*, double*, int*, double*, double*, double*, double*, double*, int*, double*)
+int srbm_qp_control_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_get_sizes(srbm_batch*, int*)
+int srbm_get_status(srbm_batch*, int*, int*)
+int srbm_get_status_accumulated(srbm_batch*, int*)
+int srbm_clear_status_accumulators(srbm_batch*)
+int srbm_get_solver_counters(srbm_batch*, long long*)
+int srbm_get_stats(srbm_batch*, double*)
+int srbm_get_qp_cost(srbm_batch*, double*)
+int srbm_get_qp_solution(srbm_batch*, double*, int)
+int srbm_get_raw_qp_minimiser(srbm_batch*, double*, int)
+int srbm_get_dual_solution(srbm_batch*, double*, double*, int)
+int srbm_get_trajectory_states(srbm_batch*, double*)
+int srbm_get_knots(srbm_batch*, int, double*, int*, int*, double*, double*, double*)
+int srbm_export_qp(srbm_batch*, int, double*, double*, double*, double*)
+int srbm_result_record_doubles(int)
+int srbm_pack_results_dev(srbm_batch*, dev*, int)
+int srbm_pack_results(srbm_batch*, double*, int)
+int srbm_allgather_results(srbm_batch*, ncclComm_t, dev*)
+int srbm_rccl_get_unique_id(void*)
+int srbm_rccl_comm_init_rank(srbm_batch*, int, int, void*, ncclComm_t*)
+int srbm_rccl_comm_destroy(ncclComm_t)
+int srbm_enable_kernel_timing(srbm_batch*, int)
+int srbm_get_kernel_timing(srbm_batch*, double*, int*)
+int srbm_get_kernel_timings(srbm_batch*, double*, int, int*)
+int srbm_get_work_counters(srbm_batch*, double*, double*)
+int srbm_get_executed_mfma(srbm_batch*, double*)
+long srbm_bytes_per_instance()
+int srbm_debug_get_profile(srbm_batch*, int, double*)
+int srbm_debug_profile_slot(int, char**, char**)
+int srbm_debug_trace_field(int, char**, int*)
+int srbm_debug_solve_mapped(int, int, int*, int, double*, double*, double*, int*, double)
+int srbm_debug_solve(int, int, double*, double*, double*, double*, int*, double)
+int srbm_debug_cholesky(int, int, double*, double*, int*, double)
+int srbm_debug_sym_matvec(int, int, double*, double*, double*)
+int srbm_debug_hmatvec(int, int, double*, double*, double*)
+int srbm_debug_dense_row_placement(int, int, int, int*)
+int srbm_debug_get_trace(srbm_batch*, int, double*)
+int srbm_debug_get_spline_step(srbm_batch*, int, double*, double*, int*, int*)
+int srbm_debug_get_instance_iters(srbm_batch*, double*)
+int srbm_debug_get_launch_info(srbm_batch*, int*)''')
 
 
 def build(force=False):
@@ -112,10 +266,7 @@ def lib(large=False):
     if path not in _libs:
         if not os.path.exists(path):
             raise RuntimeError('%s is not built (run __graft_entry__.build()); there is no CPU fallback' % os.path.basename(path))
-        L = C.CDLL(path)
-        L.srbm_last_error.restype = C.c_char_p
-        L.srbm_stream.restype = C.c_void_p
-        L.srbm_bytes_per_instance.restype = C.c_long
+        L = declare(C.CDLL(path), PROTOTYPES)
         cap = (C.c_int * 4)()
         L.srbm_get_capacity(cap)
         L.capacity = dict(N=cap[0], nu=cap[1], samples=cap[2], knots=cap[3])
@@ -383,39 +534,29 @@ class BatchMPC:
 
     def eval_trajectory(self, time):
         """Trajectory::GetForce / GetEndEffectorLocation / GetContacts of every instance's current trajectory at time[batch]"""
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.batch,)))
+        t = self._times(time)
         f = np.zeros((self.batch, 4, 3)); p = np.zeros((self.batch, 4, 3)); c = np.zeros((self.batch, 4), np.int32)
         self._chk(self.L.srbm_eval_trajectory(self.h, _d(t), _d(f), _d(p), _i(c)))
         return f, p, c
 
     def ee_box_center(self):
-        a = np.zeros((4, 2))
-        self._chk(self.L.srbm_get_ee_box_center(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_ee_box_center, self.h, np.zeros((4, 2)))
 
     def cost(self):
-        a = np.zeros(self.batch)
-        self._chk(self.L.srbm_get_cost(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_cost, self.h, np.zeros(self.batch))
 
     def merit(self):
-        m = np.zeros(self.batch); d = np.zeros(self.batch)
-        self._chk(self.L.srbm_get_merit(self.h, _d(m), _d(d)))
-        return m, d
+        return self._get(self.L.srbm_get_merit, self.h, np.zeros(self.batch), np.zeros(self.batch))
 
     def add_force_cost(self, weight):
-        self._chk(self.L.srbm_add_force_cost(self.h, C.c_double(weight)))
+        self._chk(self.L.srbm_add_force_cost(self.h, weight))
 
     def avg_cost(self):
-        a = np.zeros(self.batch)
-        self._chk(self.L.srbm_get_avg_cost(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_avg_cost, self.h, np.zeros(self.batch))
 
     def status_accumulated(self):
         """sticky accumulators over all solves since the last clear: [batch][4] = error bits, solves, not-solved, of those MaxIter"""
-        a = np.zeros((self.batch, 4), np.int32)
-        self._chk(self.L.srbm_get_status_accumulated(self.h, _i(a)))
-        return a
+        return self._get(self.L.srbm_get_status_accumulated, self.h, np.zeros((self.batch, 4), np.int32))
 
     def clear_status_accumulators(self):
         self._chk(self.L.srbm_clear_status_accumulators(self.h))
@@ -462,7 +603,7 @@ class BatchMPC:
         self._chk(self.L.srbm_add_force_cost_each(self.h, int(first), len(a), _d(a)))
 
     def set_solver_step_rule(self, tol_step, start_mu=0.0):
-        self._chk(self.L.srbm_set_solver_step_rule(self.h, C.c_double(tol_step), C.c_double(start_mu)))
+        self._chk(self.L.srbm_set_solver_step_rule(self.h, tol_step, start_mu))
 
     def enable_fast_termination(self, start_mu=FAST_START_MU):
         """opt into the step rule (and, for srbm_rti_advance, the lower-start attempt) at the values the bench line is taken with"""
@@ -475,9 +616,7 @@ class BatchMPC:
 
     def solve_flags(self):
         """per instance, of the LAST solve: bit 0 ended through the step rule, bit 1 began with a lower-start attempt, bit 2 the attempt was repeated"""
-        f = np.zeros(self.batch, np.int32)
-        self._chk(self.L.srbm_get_solve_flags(self.h, _i(f)))
-        return f
+        return self._get(self.L.srbm_get_solve_flags, self.h, np.zeros(self.batch, np.int32))
 
     def solver_step_rule(self):
         a = C.c_double(0); b = C.c_double(0)
@@ -494,7 +633,19 @@ class BatchMPC:
         self._chk(self.L.srbm_set_state_trajectory_warm_start(self.h, _d(a)))
 
     def set_solver_tolerances(self, gap_abs, gap_rel, feas, max_iter=200):
-        self._chk(self.L.srbm_set_solver_tolerances(self.h, C.c_double(gap_abs), C.c_double(gap_rel), C.c_double(feas), int(max_iter)))
+        self._chk(self.L.srbm_set_solver_tolerances(self.h, gap_abs, gap_rel, feas, int(max_iter)))
+
+    def _times(self, time):             # a time, or one per instance, as time[batch]
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.batch,)))
+
+    def _get(self, fn, h, *outs, tail=()):
+        """the read-back getters: fn(h, *outs, *tail) on the caller's zeroed arrays (each passed as a pointer of its dtype), check, return them"""
+        self._chk(fn(h, *[(_i if a.dtype == np.int32 else _d)(a) for a in outs], *tail))
+        return outs[0] if len(outs) == 1 else outs
+
+    # leading dimensions of the result records with the capacities of the loaded build (include/srbm_rti.h: NX, NM of srbm_pack_results_dev)
+    _ld_primal = property(lambda self: (self.N + 1) * 12 + self.NUMAX)
+    _ld_dual = property(lambda self: (self.N + 1) * 12 + 6 * self.NSMAX + 16 * (self.N - 3) + 16)
 
     def _bcast(self, a, width):
         a = np.asarray(a, dtype=np.float64)
@@ -509,11 +660,11 @@ class BatchMPC:
 
     def get_real_time_update(self, state, init_time, ee):
         s = self._bcast(state, 13); e = self._bcast(ee, 12)
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(init_time, dtype=np.float64), (self.batch,)))
+        t = self._times(init_time)
         self._chk(self.L.srbm_get_real_time_update(self.h, _d(s), _d(t), _d(e)))
 
     def get_real_time_update_dev(self, state_ptr, time_ptr, ee_ptr):
-        self._chk(self.L.srbm_get_real_time_update_dev(self.h, C.c_void_p(state_ptr), C.c_void_p(time_ptr), C.c_void_p(ee_ptr)))
+        self._chk(self.L.srbm_get_real_time_update_dev(self.h, state_ptr, time_ptr, ee_ptr))
 
     def rti_advance(self, first_index, steps):
         self._chk(self.L.srbm_rti_advance(self.h, int(first_index), int(steps)))
@@ -526,9 +677,7 @@ class BatchMPC:
         self._chk(self.L.srbm_plant_set_state(self.h, _d(self._bcast(state, 13))))
 
     def plant_state(self):
-        out = np.zeros((self.batch, 13))
-        self._chk(self.L.srbm_plant_get_state(self.h, _d(out)))
-        return out
+        return self._get(self.L.srbm_plant_get_state, self.h, np.zeros((self.batch, 13)))
 
     def plant_set_push(self, time=None, impulse=None):
         """one push per instance: lin-mom += impulse[:3], ang-mom += impulse[3:] when the plant passes `time`; None clears"""
@@ -563,7 +712,7 @@ class BatchMPC:
     def step_log_copy_dev(self, ptr, first=0, count=None):
         """the same records to device memory at `ptr`, on the batch's stream, without synchronisation"""
         count = self.step_log_count() - first if count is None else count
-        self._chk(self.L.srbm_step_log_copy_dev(self.h, int(first), int(count), C.c_void_p(ptr)))
+        self._chk(self.L.srbm_step_log_copy_dev(self.h, int(first), int(count), ptr))
 
     def synchronize(self):
         self._chk(self.L.srbm_synchronize(self.h))
@@ -577,7 +726,7 @@ class BatchMPC:
         self._chk(self.L.srbm_update_contact_times(self.h, _d(a), a.shape[2]))
 
     def adjust_for_current_contacts(self, time, in_contact):
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.batch,)))
+        t = self._times(time)
         c = np.ascontiguousarray(np.broadcast_to(np.asarray(in_contact, dtype=np.int32), (self.batch, 4)))
         self._chk(self.L.srbm_adjust_for_current_contacts(self.h, _d(t), _i(c)))
 
@@ -597,18 +746,18 @@ class BatchMPC:
 
     def get_targets_from_traj_dev(self, time_ptr, q_des_ptr, v_des_ptr, force_des_ptr, status_ptr):
         """the same on device pointers (ints, e.g. torch tensors' data_ptr()): one launch on the batch's stream, no copy, no synchronisation"""
-        self._chk(self.L.srbm_get_targets_from_traj_dev(self.h, C.c_void_p(time_ptr), C.c_void_p(q_des_ptr), C.c_void_p(v_des_ptr), C.c_void_p(force_des_ptr), C.c_void_p(status_ptr)))
+        self._chk(self.L.srbm_get_targets_from_traj_dev(self.h, time_ptr, q_des_ptr, v_des_ptr, force_des_ptr, status_ptr))
 
     def eval_trajectory_dev(self, time_ptr, force_ptr, pos_ptr, in_contact_ptr):
         """Trajectory::GetForce / GetEndEffectorLocation / contact flags on device pointers (one launch, no copy)"""
-        self._chk(self.L.srbm_eval_trajectory_dev(self.h, C.c_void_p(time_ptr), C.c_void_p(force_ptr), C.c_void_p(pos_ptr), C.c_void_p(in_contact_ptr)))
+        self._chk(self.L.srbm_eval_trajectory_dev(self.h, time_ptr, force_ptr, pos_ptr, in_contact_ptr))
 
     def qp_control_dev(self, q, v, contact, q_des, v_des, force_des, control, qp_sol, status):
-        self._chk(self.L.srbm_qp_control_dev(self.h, *[C.c_void_p(p) for p in (q, v, contact, q_des, v_des, force_des, control, qp_sol, status)]))
+        self._chk(self.L.srbm_qp_control_dev(self.h, q, v, contact, q_des, v_des, force_des, control, qp_sol, status))
 
     def get_targets_from_traj(self, time, q_des):
         """MPCController::GetTargetsFromTraj on the current trajectories -> (q_des, v_des [batch][18], force_des [batch][4][3], status)"""
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.batch,)))
+        t = self._times(time)
         q = self._bcast(q_des, 19).copy(); v = np.zeros((self.batch, 18)); f = np.zeros((self.batch, 4, 3)); st = np.zeros(self.batch, np.int32)
         self._chk(self.L.srbm_get_targets_from_traj(self.h, _d(t), _d(q), _d(v), _d(f), _i(st)))
         return q, v, f, st
@@ -676,81 +825,61 @@ class BatchMPC:
         return it.value, fl.value
 
     def pack_results_dev(self, ptr, ld):
-        self._chk(self.L.srbm_pack_results_dev(self.h, C.c_void_p(ptr), int(ld)))
+        self._chk(self.L.srbm_pack_results_dev(self.h, ptr, int(ld)))
 
     # ---- multi-GPU: RCCL all-gather of the result records through the C-ABI (include/srbm_rti.h: srbm_allgather_results) ----
     def rccl_unique_id(self):
         """ncclGetUniqueId (one rank calls it, the 128 bytes travel to the others by the host's own rendezvous)"""
-        buf = (C.c_ubyte * 128)()
+        buf = (C.c_ubyte * RCCL_UNIQUE_ID_BYTES)()
         self._chk(self.L.srbm_rccl_get_unique_id(buf))
         return bytes(buf)
 
     def rccl_comm_init_rank(self, world, rank, id_bytes):
         """ncclCommInitRank on the batch's device; returns the ncclComm_t as an integer handle"""
-        assert len(id_bytes) == 128
+        assert len(id_bytes) == RCCL_UNIQUE_ID_BYTES
         comm = C.c_void_p(0)
-        buf = (C.c_ubyte * 128).from_buffer_copy(id_bytes)
+        buf = (C.c_ubyte * RCCL_UNIQUE_ID_BYTES).from_buffer_copy(id_bytes)
         self._chk(self.L.srbm_rccl_comm_init_rank(self.h, int(world), int(rank), buf, C.byref(comm)))
         return comm.value
 
     def rccl_comm_destroy(self, comm):
-        self._chk(self.L.srbm_rccl_comm_destroy(C.c_void_p(comm)))
+        self._chk(self.L.srbm_rccl_comm_destroy(comm))
 
     def allgather_results(self, comm, out_ptr):
         """this rank's result records packed into their slot of out[world * batch][record_doubles] (device pointer) and ONE in-place ncclAllGather
         on the batch's stream; asynchronous (synchronize() before reading)"""
-        self._chk(self.L.srbm_allgather_results(self.h, C.c_void_p(comm), C.c_void_p(out_ptr)))
+        self._chk(self.L.srbm_allgather_results(self.h, comm, out_ptr))
 
     def pack_results(self):
         """the result records of srbm_pack_results_dev in a host array [batch][srbm_result_record_doubles(N)]"""
         ld = self.result_record_doubles()
-        a = np.zeros((self.batch, ld))
-        self._chk(self.L.srbm_pack_results(self.h, _d(a), ld))
-        return a
+        return self._get(self.L.srbm_pack_results, self.h, np.zeros((self.batch, ld)), tail=(ld,))
 
     # ---- results ----
     def sizes(self):
-        a = np.zeros((self.batch, 8), np.int32)
-        self._chk(self.L.srbm_get_sizes(self.h, _i(a)))
-        return a
+        return self._get(self.L.srbm_get_sizes, self.h, np.zeros((self.batch, 8), np.int32))
 
     def status(self):
-        s = np.zeros(self.batch, np.int32); e = np.zeros(self.batch, np.int32)
-        self._chk(self.L.srbm_get_status(self.h, _i(s), _i(e)))
-        return s, e
+        return self._get(self.L.srbm_get_status, self.h, np.zeros(self.batch, np.int32), np.zeros(self.batch, np.int32))
 
     def stats(self):
-        a = np.zeros((self.batch, 8))
-        self._chk(self.L.srbm_get_stats(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_stats, self.h, np.zeros((self.batch, 8)))
 
     def qp_cost(self):
-        a = np.zeros(self.batch)
-        self._chk(self.L.srbm_get_qp_cost(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_qp_cost, self.h, np.zeros(self.batch))
 
     def qp_solution(self):
-        ld = (self.N + 1) * 12 + self.NUMAX
-        a = np.zeros((self.batch, ld))
-        self._chk(self.L.srbm_get_qp_solution(self.h, _d(a), ld))
-        return a
+        return self._get(self.L.srbm_get_qp_solution, self.h, np.zeros((self.batch, self._ld_primal)), tail=(self._ld_primal,))
 
     def raw_qp_minimiser(self):
-        ld = (self.N + 1) * 12 + self.NUMAX
-        a = np.zeros((self.batch, ld))
-        self._chk(self.L.srbm_get_raw_qp_minimiser(self.h, _d(a), ld))
-        return a
+        return self._get(self.L.srbm_get_raw_qp_minimiser, self.h, np.zeros((self.batch, self._ld_primal)), tail=(self._ld_primal,))
 
     def dual_solution(self):
-        ld = (self.N + 1) * 12 + 6 * self.NSMAX + 16 * (self.N - 3) + 16
-        z = np.zeros((self.batch, ld)); s = np.zeros((self.batch, ld))
-        self._chk(self.L.srbm_get_dual_solution(self.h, _d(z), _d(s), ld))
-        return z, s
+        ld = self._ld_dual
+        return self._get(self.L.srbm_get_dual_solution, self.h, np.zeros((self.batch, ld)), np.zeros((self.batch, ld)), tail=(ld,))
 
     def trajectory_states(self):
-        a = np.zeros((self.batch, self.N + 1, 13))
-        self._chk(self.L.srbm_get_trajectory_states(self.h, _d(a)))
-        return a
+        return self._get(self.L.srbm_get_trajectory_states, self.h, np.zeros((self.batch, self.N + 1, 13)))
 
     def knots(self, inst):
         t = np.zeros((4, 32)); kd = np.zeros((4, 32), np.int32); nk = np.zeros(4, np.int32)
@@ -806,39 +935,31 @@ class BatchGaitOptimizer:
         self.mpc._chk(self.L.srbm_gait_set_contact_times_from_trajectory(self.g))
 
     def contact_times(self):
-        xk = np.zeros((self.mpc.batch, self.NV)); counts = np.zeros((self.mpc.batch, 4), np.int32)
-        self.mpc._chk(self.L.srbm_gait_get_contact_times(self.g, _d(xk), _i(counts)))
-        return xk, counts
+        return self.mpc._get(self.L.srbm_gait_get_contact_times, self.g, np.zeros((self.mpc.batch, self.NV)), np.zeros((self.mpc.batch, 4), np.int32))
 
     def compute_sensitivity(self):
         self.mpc._chk(self.L.srbm_gait_compute_sensitivity(self.g))
 
     def sensitivity(self):
         m = self.mpc
-        ld = (m.N + 1) * 12 + m.NUMAX + 6 * m.NSMAX + 16 * (m.N - 3) + (m.N + 1) * 12 + 16
-        d = np.zeros((m.batch, ld))
-        m._chk(self.L.srbm_gait_get_sensitivity(self.g, _d(d), ld))
-        return d
+        ld = m._ld_primal + m._ld_dual           # [dz; dlam; dnu]: one entry per primal and per dual variable
+        return m._get(self.L.srbm_gait_get_sensitivity, self.g, np.zeros((m.batch, ld)), tail=(ld,))
 
     def compute_gradient(self):
         self.mpc._chk(self.L.srbm_gait_compute_gradient(self.g))
 
     def gradient(self):
         m = self.mpc
-        g = np.zeros((m.batch, self.NV)); valid = np.zeros(m.batch, np.int32)
-        m._chk(self.L.srbm_gait_get_gradient(self.g, _d(g), _i(valid)))
-        return g, valid
+        return m._get(self.L.srbm_gait_get_gradient, self.g, np.zeros((m.batch, self.NV)), np.zeros(m.batch, np.int32))
 
     def optimize_contact_times(self, time):
         m = self.mpc
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (m.batch,)))
+        t = m._times(time)
         m._chk(self.L.srbm_gait_optimize_contact_times(self.g, _d(t)))
 
     def lp_result(self):
         m = self.mpc
-        st = np.zeros(m.batch, np.int32); pr = np.zeros(m.batch)
-        m._chk(self.L.srbm_gait_get_lp_result(self.g, _i(st), _d(pr)))
-        return st, pr
+        return m._get(self.L.srbm_gait_get_lp_result, self.g, np.zeros(m.batch, np.int32), np.zeros(m.batch))
 
     def rti_advance(self, first_run_num, steps, gait_opt_freq):
         self.mpc._chk(self.L.srbm_gait_rti_advance(self.g, int(first_run_num), int(steps), int(gait_opt_freq)))
@@ -850,21 +971,18 @@ class BatchGaitOptimizer:
         self.mpc._chk(self.L.srbm_gait_set_step(self.g, _d(a)))
 
     def step(self):
-        a = np.zeros((self.mpc.batch, self.NV))
-        self.mpc._chk(self.L.srbm_gait_get_step(self.g, _d(a)))
-        return a
+        return self.mpc._get(self.L.srbm_gait_get_step, self.g, np.zeros((self.mpc.batch, self.NV)))
 
     def line_search(self, state, init_time, ee):
         m = self.mpc
         s = m._bcast(state, 13); e = m._bcast(ee, 12)
-        t = np.ascontiguousarray(np.broadcast_to(np.asarray(init_time, dtype=np.float64), (m.batch,)))
+        t = m._times(init_time)
         imin = np.zeros(m.batch, np.int32); costs = np.zeros((m.batch, self.LS_SIZE))
         m._chk(self.L.srbm_gait_line_search(self.g, _d(s), _d(t), _d(e), _i(imin), _d(costs)))
         return imin, costs
 
     def candidates(self):
         """the candidate batch of the last line search as a BORROWED BatchMPC view (read-back entries only): candidate c of instance b at b * 10 + c"""
-        self.L.srbm_gait_debug_candidates.restype = C.c_void_p
         v = object.__new__(BatchMPC)
         m = self.mpc
         v.N, v.large, v.L, v.NUMAX, v.NSMAX, v.cfg = m.N, m.large, m.L, m.NUMAX, m.NSMAX, m.cfg
@@ -875,8 +993,7 @@ class BatchGaitOptimizer:
 
     def candidate_status(self):
         n = self.mpc.batch * self.LS_SIZE
-        st = np.zeros(n, np.int32); err = np.zeros(n, np.int32)
-        self.mpc._chk(self.L.srbm_gait_get_candidate_status(self.g, _i(st), _i(err)))
+        st, err = self.mpc._get(self.L.srbm_gait_get_candidate_status, self.g, np.zeros(n, np.int32), np.zeros(n, np.int32))
         return st.reshape(-1, self.LS_SIZE), err.reshape(-1, self.LS_SIZE)
 
 

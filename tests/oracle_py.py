@@ -6,6 +6,8 @@ import subprocess
 
 import numpy as np
 
+from srbm_loader.host import C_TYPES, declare, prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, 'oracle')
 CONFIG_DIR = os.path.join(ROOT, 'bilevel-gait-gen_amd', 'configs')
@@ -29,6 +31,66 @@ class OrcConfig(C.Structure):
                 ('Q_diag', C.c_double * 12), ('des_state', C.c_double * 13)]
 
 
+# every function of oracle/oracle_capi.cpp in the spelling of host.PROTOTYPES (handles are void*); tests/test_abi_prototypes.py holds the table to
+# that file and to the symbols of liboracle.so
+PROTOTYPES = prototypes('''\
+void* orc_mpc_create(orc_config*)
+void orc_mpc_destroy(void*)
+void* orc_mpc_clone(void*)
+char* orc_mpc_error(void*)
+void orc_mpc_set_warmstart(void*, double*)
+int orc_mpc_initial_run(void*, double*, double*)
+int orc_mpc_solve(void*, double*, double, double*)
+int orc_mpc_rti(void*, double*, double, double*)
+void orc_mpc_set_max_iter(void*, int)
+void orc_mpc_sizes(void*, int*)
+void orc_mpc_get_x(void*, double*)
+void orc_mpc_get_qp_x(void*, double*)
+void orc_mpc_get_z(void*, double*)
+void orc_mpc_get_s(void*, double*)
+void orc_mpc_get_states(void*, double*)
+void orc_mpc_get_stats(void*, double*)
+void orc_mpc_get_qp_dense(void*, double*, double*, double*, double*)
+int orc_mpc_constraint_nnz(void*)
+int orc_mpc_get_knots(void*, int, double*, int*, int*, double*, int*, double*)
+double orc_mpc_init_time(void*)
+int orc_mpc_get_contact_times(void*, int, double*, int*)
+int orc_mpc_set_contact_times(void*, int, int*, double*)
+int orc_mpc_adjust_for_current_contacts(void*, double, int*)
+double orc_mpc_ee_value(void*, int, int, int, double)
+int orc_mpc_plant_integrate(void*, double*, double, double, int, int, double*)
+int orc_gait_gradient(void*, double*)
+int orc_gait_get_d(void*, double*)
+int orc_gait_param_partials(void*, void*, int, int, double*, double*, double*, double*)
+int orc_gait_optimize(void*, double, double*, double*)
+int orc_gait_line_search(void*, double*, double, double*, double*)
+int orc_gait_line_search_q(void*, double*, double, double*, double*, int*)
+int orc_qp_solve(int, int, int, int*, int*, double*, double*, int, int*, int*, double*, double*, int, int*, int*, double, double, double*, double*, double*, int*)
+void orc_qp_sensitivity(int, int, int, double*, double*, double*, double*, double*, double*, double*, double*, double*, double*, double*)
+void* orc_spline_create(int, double*, int, int)
+void* orc_spline_clone(void*)
+void orc_spline_destroy(void*)
+double orc_spline_value_at(void*, int, int, double)
+int orc_spline_lin(void*, int, int, double, double*)
+int orc_spline_vars_idx(void*, int, int, double, int*)
+int orc_spline_is_force_mutable(void*, double)
+void orc_spline_add_poly(void*, double)
+int orc_spline_remove_poly(void*, double)
+int orc_spline_set_vars(void*, int, int, int, double, double)
+int orc_spline_mutable_nodes(void*, int, int, int*)
+int orc_spline_times(void*, double*, int*)
+int orc_spline_node_type(void*, int, int, int)
+int orc_spline_qp_vec(void*, int, int, double*)
+double orc_spline_end_time(void*)
+double orc_spline_start_time(void*)
+int orc_spline_contact_times(void*, double*)
+int orc_spline_set_contact_times(void*, int, double*)
+double orc_spline_partial_wrt_time(void*, int, int, double, int)
+int orc_spline_coef_partial_wrt_time(void*, int, int, double, int, double, double*)
+void orc_quat_exp3(double*, double*)
+void orc_quat_log3(double*, double*)''', dict(C_TYPES, **{'orc_config*': C.POINTER(OrcConfig)}))
+
+
 def load_config(name='a1_configuration', **overrides):
     cfg = json.load(open(os.path.join(CONFIG_DIR, name + '.json')))
     cfg.update(overrides)
@@ -49,16 +111,7 @@ def lib():
         path = os.path.join(ORACLE_DIR, 'liboracle.so')
         if not os.path.exists(path):
             build_oracle()
-        L = C.CDLL(path)
-        L.orc_mpc_create.restype = C.c_void_p
-        L.orc_mpc_clone.restype = C.c_void_p
-        L.orc_mpc_error.restype = C.c_char_p
-        L.orc_spline_create.restype = C.c_void_p
-        L.orc_spline_clone.restype = C.c_void_p
-        for f in ('orc_spline_value_at', 'orc_spline_end_time', 'orc_spline_start_time', 'orc_spline_partial_wrt_time',
-                  'orc_mpc_ee_value', 'orc_mpc_init_time'):
-            getattr(L, f).restype = C.c_double
-        _lib = L
+        _lib = declare(C.CDLL(path), PROTOTYPES)
     return _lib
 
 
@@ -119,12 +172,12 @@ class OracleMPC:
     def solve(self, state13, t, ee):
         s = np.ascontiguousarray(state13, dtype=np.float64)
         e = np.ascontiguousarray(ee, dtype=np.float64).reshape(-1)
-        return self._chk(self.L.orc_mpc_solve(self.h, _d(s), C.c_double(t), _d(e)))
+        return self._chk(self.L.orc_mpc_solve(self.h, _d(s), t, _d(e)))
 
     def rti(self, state13, t, ee):
         s = np.ascontiguousarray(state13, dtype=np.float64)
         e = np.ascontiguousarray(ee, dtype=np.float64).reshape(-1)
-        return self._chk(self.L.orc_mpc_rti(self.h, _d(s), C.c_double(t), _d(e)))
+        return self._chk(self.L.orc_mpc_rti(self.h, _d(s), t, _d(e)))
 
     def set_max_iter(self, it):
         self.L.orc_mpc_set_max_iter(self.h, int(it))
@@ -222,15 +275,15 @@ class OracleMPC:
 
     def adjust_for_current_contacts(self, t, in_contact):
         c = np.ascontiguousarray(in_contact, dtype=np.int32)
-        return self._chk(self.L.orc_mpc_adjust_for_current_contacts(self.h, C.c_double(t), _i(c)))
+        return self._chk(self.L.orc_mpc_adjust_for_current_contacts(self.h, t, _i(c)))
 
     def ee_value(self, ee, is_position, coord, t):
-        return self.L.orc_mpc_ee_value(self.h, ee, int(is_position), coord, C.c_double(t))
+        return self.L.orc_mpc_ee_value(self.h, ee, int(is_position), coord, t)
 
     def plant_integrate(self, state13, t, dt, num_steps, advance_time=0):
         """RKIntegrator::CalcIntegral (rk_integrator.cpp:14-30) under the current trajectory"""
         out = np.zeros(13)
-        self._chk(self.L.orc_mpc_plant_integrate(self.h, _d(np.ascontiguousarray(state13, float)), C.c_double(t), C.c_double(dt),
+        self._chk(self.L.orc_mpc_plant_integrate(self.h, _d(np.ascontiguousarray(state13, float)), t, dt,
                                                  int(num_steps), int(advance_time), _d(out)))
         return out
 
@@ -257,14 +310,14 @@ class OracleMPC:
 
     def gait_optimize(self, time):
         step = np.zeros(128); new = np.zeros(128)
-        self._chk(self.L.orc_gait_optimize(self.h, C.c_double(time), _d(step), _d(new)))
+        self._chk(self.L.orc_gait_optimize(self.h, time, _d(step), _d(new)))
         return step, new
 
     def gait_line_search(self, state13, t, ee):
         s = np.ascontiguousarray(state13, dtype=np.float64)
         e = np.ascontiguousarray(ee, dtype=np.float64).reshape(-1)
         costs = np.zeros(10)
-        k = self._chk(self.L.orc_gait_line_search(self.h, _d(s), C.c_double(t), _d(e), _d(costs)))
+        k = self._chk(self.L.orc_gait_line_search(self.h, _d(s), t, _d(e), _d(costs)))
         return k, costs
 
     def gait_line_search_with_quality(self, state13, t, ee):
@@ -272,7 +325,7 @@ class OracleMPC:
         s = np.ascontiguousarray(state13, dtype=np.float64)
         e = np.ascontiguousarray(ee, dtype=np.float64).reshape(-1)
         costs = np.zeros(10); q = np.zeros(10, np.int32)
-        k = self._chk(self.L.orc_gait_line_search_q(self.h, _d(s), C.c_double(t), _d(e), _d(costs), _i(q)))
+        k = self._chk(self.L.orc_gait_line_search_q(self.h, _d(s), t, _d(e), _d(costs), _i(q)))
         return k, costs, q
 
 
@@ -308,7 +361,7 @@ def qp_solve(P, q, A, b, cones, tol_gap=1e-8, tol_feas=1e-8):
     cn = np.array([c[0] for c in cones], np.int32); cd = np.array([c[1] for c in cones], np.int32)
     x = np.zeros(n); z = np.zeros(m); s = np.zeros(m); it = C.c_int(0)
     st = L.orc_qp_solve(n, m, len(pv), _i(pr), _i(pc), _d(pv), _d(q), len(av), _i(ar), _i(ac), _d(av), _d(b), len(cones),
-                        _i(cn), _i(cd), C.c_double(tol_gap), C.c_double(tol_feas), _d(x), _d(z), _d(s), C.byref(it))
+                        _i(cn), _i(cd), tol_gap, tol_feas, _d(x), _d(z), _d(s), C.byref(it))
     return dict(status=st, x=x, z=z, s=s, iters=it.value)
 
 
@@ -344,33 +397,33 @@ class OracleSpline:
             pass
 
     def value_at(self, ty, coord, t):
-        return self.L.orc_spline_value_at(self.h, ty, coord, C.c_double(t))
+        return self.L.orc_spline_value_at(self.h, ty, coord, t)
 
     def lin(self, ty, coord, t):
         out = np.zeros(8)
-        k = self.L.orc_spline_lin(self.h, ty, coord, C.c_double(t), _d(out))
+        k = self.L.orc_spline_lin(self.h, ty, coord, t, _d(out))
         if k < 0:
             raise RuntimeError('no mutable variables')
         return out[:k].copy()
 
     def vars_idx(self, ty, coord, t):
         idx = C.c_int(0)
-        k = self.L.orc_spline_vars_idx(self.h, ty, coord, C.c_double(t), C.byref(idx))
+        k = self.L.orc_spline_vars_idx(self.h, ty, coord, t, C.byref(idx))
         if k < 0:
             raise RuntimeError('no mutable variables')
         return idx.value, k
 
     def is_force_mutable(self, t):
-        return bool(self.L.orc_spline_is_force_mutable(self.h, C.c_double(t)))
+        return bool(self.L.orc_spline_is_force_mutable(self.h, t))
 
     def add_poly(self, dt):
-        self.L.orc_spline_add_poly(self.h, C.c_double(dt))
+        self.L.orc_spline_add_poly(self.h, dt)
 
     def remove_poly(self, t):
-        return self.L.orc_spline_remove_poly(self.h, C.c_double(t))
+        return self.L.orc_spline_remove_poly(self.h, t)
 
     def set_vars(self, ty, coord, node, a, b):
-        rc = self.L.orc_spline_set_vars(self.h, ty, coord, int(node), C.c_double(a), C.c_double(b))
+        rc = self.L.orc_spline_set_vars(self.h, ty, coord, int(node), a, b)
         if rc < 0:
             raise RuntimeError('set_vars failed')
 
@@ -410,11 +463,11 @@ class OracleSpline:
             raise RuntimeError('set_contact_times failed %d' % rc)
 
     def partial_wrt_time(self, ty, coord, t, idx):
-        return self.L.orc_spline_partial_wrt_time(self.h, ty, coord, C.c_double(t), idx)
+        return self.L.orc_spline_partial_wrt_time(self.h, ty, coord, t, idx)
 
     def coef_partial_wrt_time(self, ty, coord, t, idx, dtwdth=0.0):
         out = np.zeros(8)
-        k = self.L.orc_spline_coef_partial_wrt_time(self.h, ty, coord, C.c_double(t), idx, C.c_double(dtwdth), _d(out))
+        k = self.L.orc_spline_coef_partial_wrt_time(self.h, ty, coord, t, idx, dtwdth, _d(out))
         if k < 0:
             raise RuntimeError('coef partial failed')
         return out[:k].copy()

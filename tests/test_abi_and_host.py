@@ -25,7 +25,7 @@ def declared_symbols():
 
 def test_library_exports_every_declared_symbol(libpath):
     names = declared_symbols()
-    assert len(names) >= 60
+    assert len(names) >= 60 and set(names) <= set(host.PROTOTYPES)         # ... and the binding types every one of them (test_abi_prototypes.py)
     for path in (libpath, host.LIB_PATH_LARGE):        # the standard and the LARGE-capacity build carry the same C-ABI
         L = ctypes.CDLL(path)
         for n in names:
