@@ -1345,7 +1345,8 @@ int srbm_get_knots(srbm_batch* h, int inst, double* times, int* kinds, int* nk, 
     return 0;
 }
 
-// Dense expansion of the structured QP into the reference's row/column layout.
+// Dense expansion of the structured QP into the reference's row/column layout.  Its dynamics rows are the host's
+// statement of the model that csrc/srbm_lin.hiph holds for the device.
 int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* Pm, double* q) {
     if (!h || inst < 0 || inst >= h->batch) return fail("bad arguments");
     std::vector<SrbmInst> vi(1);

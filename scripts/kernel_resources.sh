@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: scripts/kernel_resources.sh bilevel-gait-gen_amd/libsrbm_rti.so  -> per kernel of EVERY gfx950 code object of the library (one per .hip
-# source: srbm_capi.hip, which includes the kernels of csrc/*.hiph -- the IPM's are srbm_k3_lds / _rows / _normal / _ipm.hiph): VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, static LDS and a short
+# source: srbm_capi.hip, which includes the kernels of csrc/*.hiph -- the IPM's are srbm_k3_lds / _rows / _normal / _ipm.hiph, the gait step's srbm_gait_candidates / _sens / _grad / _lp.hiph, the linearised model srbm_lin.hiph): VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, static LDS and a short
 # hash of its disassembly; per out-of-line device function the hash alone.  Lines sorted by name.  The hash drops the `//` comments (addresses,
 # encodings) and masks the literal of every s_add_u32 / s_addc_u32 within three instructions after an s_getpc_b64: those are PC-relative
 # offsets, which change whenever any function moves in the code object; trailing s_nop padding is dropped too.  Two builds whose outputs

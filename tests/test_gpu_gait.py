@@ -12,11 +12,11 @@ from srbm_loader.workloads import EE_NOMINAL, config_c_instance, instances
 pytestmark = pytest.mark.gpu
 
 
-def run_pair(cfgname, nsteps, batch=2, tol=1e-15):
+def run_pair(cfgname, nsteps, batch=2, tol=1e-15, large=False):
     """GPU batch + oracle brought to the same point of an open-loop RTI run (test/gait_opt_playground.cpp:113-126)"""
     cfg = load_config(cfgname)
     s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC(cfg, batch)
+    g = host.BatchMPC(cfg, batch, large=large)
     g.set_state_trajectory_warm_start(s0)
     g.set_solver_tolerances(tol, tol, 1e-10, 200)
     g.set_solver_step_rule(0.0, 0.0)        # the caller drives the protocol here: the solves it differentiates run to the gap criterion (include/srbm_rti.h)
@@ -95,14 +95,19 @@ def as_coded_sensitivity(A, P, q, xs, z, s, nx, mi):
     return sol, live, lam
 
 
-@pytest.mark.parametrize('cfgname,nsteps', [('a1_configuration', 3), ('a1_configuration', 8), ('a1_gait_opt_config', 2)])
-def test_kkt_sensitivity(cfgname, nsteps):
+@pytest.mark.parametrize('cfgname,nsteps,large', [('a1_configuration', 3, False), ('a1_configuration', 8, False), ('a1_gait_opt_config', 2, False),
+                                                  ('a1_configuration', 3, True)],
+                         ids=['a1_configuration-3', 'a1_configuration-8', 'a1_gait_opt_config-2', 'a1_configuration-3-large'])
+def test_kkt_sensitivity(cfgname, nsteps, large):
     """a12: d = [dz; dlam; dnu] of clarabel_interface.cpp:262-612 (as coded, +diag(s)).  The device solves it in the
     condensed coordinates; (1) that must equal the full-space system solved densely in numpy on the SAME QP, solution
     and multipliers (tight); (2) against the oracle only the well-posed parts are compared: with exact complementarity
     the system's solution is (0, 1, nu), what remains is -s_i on degenerate rows (lambda_i and s_i both ~ sqrt(mu)),
-    whose size is a property of the interior-point path of each solver, not of the QP."""
-    cfg, g, o, state, ee, t = run_pair(cfgname, nsteps)
+    whose size is a property of the interior-point path of each solver, not of the QP.
+    large: the LARGE build keeps a 112 x 112 block of the LU in LDS; at n_u = 120 the first eight elimination steps run on the copy in L2 and
+    the last eight rows of the back substitution are block-wide dot products -- the path no standard-build configuration takes.  Part (1) and
+    a factorisation that did not fail; part (2) stays with the standard build."""
+    cfg, g, o, state, ee, t = run_pair(cfgname, nsteps, large=large)
     assert o.stats()['status'] == 0 and g.status()[0][0] == 0
     assert o.gait_gradient() is not None
     do = o.gait_d()
@@ -112,6 +117,8 @@ def test_kkt_sensitivity(cfgname, nsteps):
     sz = o.sizes()
     n, mi, me = sz['n'], sz['n_ineq'], sz['n_eq']
     nx = (cfg['num_nodes'] + 1) * 12
+    if large:
+        assert n - nx > 112              # n_u beyond KG_LMAX of the LARGE build (csrc/srbm_gait_sens.hiph): the L2 steps run
     assert np.array_equal(d[0], d[1])
     dz, dl, dn = d[0, :n], d[0, n:n + mi], d[0, n + mi:n + mi + me]
     # (1) same linear system, same data, dense full-space solve
@@ -136,6 +143,10 @@ def test_kkt_sensitivity(cfgname, nsteps):
     assert np.abs(r1).max() <= 1e-5 * max(1.0, np.abs(dldx).max())
     assert np.abs(G @ dz + s[0, ineq] * dl)[live].max() <= 1e-9
     assert np.abs(Ae @ dz).max() <= 1e-9
+    if large:
+        gait.compute_gradient()
+        assert gait.gradient()[1][0] == 1       # valid: among its conditions lu_fail == 0
+        return
     # (2) oracle: dq = dz + x*, dh = -lam o dlam, db = -dnu (the QP partials the gradient is built from)
     xo = o.x(); lam_o = o.z()[nx:nx + mi]
     s_o = o.s()[nx:nx + mi]
