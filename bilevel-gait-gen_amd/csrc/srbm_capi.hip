@@ -999,6 +999,14 @@ int srbm_gait_get_gradient(srbm_gait* g, double* dHdth, int* valid) {
     const size_t B = g->h->batch;
     return fetch(g->h, {{dHdth, g->dHdth, sizeof(double) * SRBM_GAIT_NV * B}, {valid, g->valid, sizeof(int) * B}});
 }
+int srbm_gait_set_gradient(srbm_gait* g, const double* dHdth, const int* valid) {
+    if (!g || !dHdth || !valid) return fail("bad arguments");
+    const size_t B = g->h->batch;
+    HIPCHK(hipSetDevice(g->h->device));
+    HIPCHK(hipMemcpyAsync(g->dHdth, dHdth, sizeof(double) * SRBM_GAIT_NV * B, hipMemcpyHostToDevice, g->h->stream));
+    HIPCHK(hipMemcpyAsync(g->valid, valid, sizeof(int) * B, hipMemcpyHostToDevice, g->h->stream));
+    return srbm_synchronize(g->h);
+}
 int srbm_gait_get_sensitivity(srbm_gait* g, double* d, int ld) {
     if (!g || !d || ld <= 0) return fail("bad arguments");
     srbm_batch* h = g->h;

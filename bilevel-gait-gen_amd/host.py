@@ -186,6 +186,7 @@ int srbm_gait_compute_sensitivity(srbm_gait*)
 int srbm_gait_get_sensitivity(srbm_gait*, double*, int)
 int srbm_gait_compute_gradient(srbm_gait*)
 int srbm_gait_get_gradient(srbm_gait*, double*, int*)
+int srbm_gait_set_gradient(srbm_gait*, double*, int*)
 int srbm_gait_get_param_partials(srbm_batch*, int, int, int, double*, double*, double*, double*)
 int srbm_gait_optimize_contact_times(srbm_gait*, double*)
 int srbm_gait_get_lp_result(srbm_gait*, int*, double*)
@@ -951,6 +952,14 @@ class BatchGaitOptimizer:
     def gradient(self):
         m = self.mpc
         return m._get(self.L.srbm_gait_get_gradient, self.g, np.zeros((m.batch, self.NV)), np.zeros(m.batch, np.int32))
+
+    def set_gradient(self, dHdth, valid=1):
+        """a gradient supplied by the caller: dHdth[batch][<= 32] (or one row for every instance), valid[batch] (or one value)"""
+        a = np.zeros((self.mpc.batch, self.NV))
+        gr = np.asarray(dHdth, dtype=np.float64)
+        a[:, :gr.shape[-1]] = gr
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(valid, dtype=np.int32), (self.mpc.batch,)))
+        self.mpc._chk(self.L.srbm_gait_set_gradient(self.g, _d(a), _i(v)))
 
     def optimize_contact_times(self, time):
         m = self.mpc

@@ -264,6 +264,9 @@ int srbm_gait_get_sensitivity(srbm_gait* g, double* d, int ld);
  * valid[batch] = 0 where the reference refuses (last QP not Solved, mpc.cpp:1048) -- may be NULL */
 int srbm_gait_compute_gradient(srbm_gait* g);
 int srbm_gait_get_gradient(srbm_gait* g, double* dHdth, int* valid);
+/* a gradient supplied by the caller (the twin of srbm_gait_set_step): dHdth[batch][32], valid[batch]; what srbm_gait_optimize_contact_times
+ * then minimises and srbm_gait_rti_advance's deriv_ready reads */
+int srbm_gait_set_gradient(srbm_gait* g, const double* dHdth, const int* valid);
 /* MPCSingleRigidBody::ComputeParamPartialsClarabel (mpc/mpc_single_rigid_body.cpp:642-792; read as matrices at test/mpc_test.cpp:181-184 and
  * mpc/gait_optimizer.cpp:92-179): partials of the QP of the last solve of instance `inst` w.r.t. contact time `idx` of foot `ee`, on the instance's
  * current trajectory, dense, in the layout of mpc::QPPartials (mpc/include/qp/qp_partials.h:15-35): dA [n_eq][n], dG [n_ineq][n], db [n_eq],

@@ -304,7 +304,7 @@ def test_every_public_method_converts_under_the_declared_types(monkeypatch):
     go = host.BatchGaitOptimizer(g)
     go.g = C.c_void_p(HANDLE)
     gait_cases = {'set_contact_times_from_trajectory': [()], 'contact_times': [()], 'compute_sensitivity': [()], 'sensitivity': [()],
-                  'compute_gradient': [()], 'gradient': [()], 'optimize_contact_times': [(0.25,), (np.full(B, 0.25),)], 'lp_result': [()],
+                  'compute_gradient': [()], 'gradient': [()], 'set_gradient': [(np.zeros(8),), (np.zeros((B, 32)), np.ones(B, np.int32))], 'optimize_contact_times': [(0.25,), (np.full(B, 0.25),)], 'lp_result': [()],
                   'rti_advance': [(0, 10, 5)], 'set_step': [(np.zeros(8),), (np.zeros((B, 32)),)], 'step': [()],
                   'line_search': [(s0, 0.25, ee), (S, np.full(B, 0.25), EE)], 'candidates': [()], 'candidate_status': [()]}
     assert set(gait_cases) | {'close'} == public_methods(host.BatchGaitOptimizer)
