@@ -15,6 +15,7 @@
 #include "srbm_gait.hiph"
 #include "srbm_plant.hiph"
 #include "srbm_fused.hiph"
+#include "srbm_gait_rollout.hiph"
 #include "srbm_ik.hiph"
 #include "srbm_wbc.hiph"
 #include "srbm_batch.hiph"
@@ -1110,6 +1111,77 @@ int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_o
         HIPCHK(hipGetLastError());
     }
     return 0;
+}
+// ---- closed-loop rollout with the gait step (include/srbm_rti.h; srbm_gait_rollout.hiph) ----
+static SrbmPlantArgs plant_args(const srbm_batch* h, int substeps, int advance_time) {
+    return SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push_time : nullptr, h->push_set ? h->d_push_impulse : nullptr, substeps, advance_time ? 1 : 0};
+}
+// the plant half of closed-loop iteration `index` on its own kernel: h->d_plant advanced, h->d_state / d_time / d_ee filled
+static int launch_plant(srbm_batch* h, int index, int substeps, int advance_time) {
+    const SrbmPlantArgs pl = plant_args(h, substeps, advance_time);
+    hipLaunchKernelGGL(srbm_k_plant_inputs, dim3(h->batch), dim3(GR_PLANT_THREADS), 0, h->stream, h->dp, h->insts, index * h->hp.dt, pl.substeps, pl.advance_time,
+                       pl.plant, pl.push_time, pl.push_impulse, h->d_state, h->d_time, h->d_ee);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_plant_advance(srbm_batch* h, int index, int substeps, int advance_time, double* state, double* time, double* ee) {
+    if (!h || substeps < 1) return fail("srbm_plant_advance: bad arguments");
+    if (!h->d_plant) return fail("srbm_plant_advance: the plant state has not been set (srbm_plant_set_state)");
+    if (use_batch(h) || launch_plant(h, index, substeps, advance_time)) return -1;
+    const size_t B = h->batch;
+    return fetch(h, {{state, h->d_state, sizeof(double) * 13 * B}, {time, h->d_time, sizeof(double) * B}, {ee, h->d_ee, sizeof(double) * 12 * B}});
+}
+// the record of the gradient or line-search run just queued (srbm_k_gait_step_log)
+static int log_gait_step(srbm_gait* g, int run) {
+    srbm_batch* h = g->h;
+    if (!h->d_log) return 0;
+    hipLaunchKernelGGL(srbm_k_gait_step_log, dim3(h->batch), dim3(64), 0, h->stream, h->insts, h->d_state, h->d_time, h->d_ee, log_args(h), run, g->ready,
+                       g->lp_status, g->pred_red, g->imin, g->costs);
+    HIPCHK(hipGetLastError());
+    h->log_used++;
+    return 0;
+}
+// The controller loop of srbm_gait_rti_advance closed over the plant of srbm_closed_loop_advance: run r integrates the plant from (r - 1) dt to r dt
+// (iteration r - 1 of srbm_closed_loop_advance) and branches on r as srbm_gait_rti_advance does.  A maximal stretch of plain runs is ONE multi-step plant
+// launch (launch_fused: the step queues for a batch larger than the chip); gradient and line-search runs take the plant kernel, then the one-step kernels.
+int srbm_gait_closed_loop_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq, int substeps, int advance_time) {
+    const char* fn = "srbm_gait_closed_loop_advance";
+    if (!g) return fail(std::string(fn) + ": bad arguments (NULL handle)");
+    srbm_batch* h = g->h;
+    if (first_run_num < 1) return fail(std::string(fn) + ": first_run_num must be at least 1 (run r integrates the plant from (r - 1) dt to r dt)");
+    if (steps < 0 || gait_opt_freq <= 0 || substeps < 1) return fail(std::string(fn) + ": bad arguments (steps >= 0, gait_opt_freq > 0, substeps >= 1)");
+    if (!h->d_plant) return fail(std::string(fn) + ": the plant state has not been set (srbm_plant_set_state)");
+    if (log_room(h, fn, steps)) return -1;
+    if (use_batch(h)) return -1;
+    const int F = gait_opt_freq, end = first_run_num + steps;
+    auto plain = [F](int r) { return r % F != 0 && (r + 1) % F != 0; };
+    for (int r = first_run_num; r < end;) {
+        if (plain(r)) {
+            int n = 1;
+            while (r + n < end && plain(r + n)) n++;
+            if (launch_fused(h, fn, r - 1, n, plant_args(h, substeps, advance_time))) return -1;
+            launch_gait_ready(g, 0);
+            r += n;
+        } else if (r % F == 0) {
+            // instances without a ready gradient get the plain update through the same 10-candidate batch (zero step)
+            if (launch_plant(h, r - 1, substeps, advance_time) || line_search_core(g, true)) return -1;
+            if (log_gait_step(g, SRBM_GAIT_RUN_LINE_SEARCH)) return -1;          // before the flag is reset: it tells who searched
+            launch_gait_ready(g, 0);
+            r++;
+        } else {
+            // the solve the gradient differentiates: to the gap criterion whatever the batch's step rule says (srbm_gait_rti_advance)
+            if (launch_plant(h, r - 1, substeps, advance_time) || launch_step(h, true) || gait_opt_core(g)) return -1;
+            if (log_gait_step(g, SRBM_GAIT_RUN_GRADIENT)) return -1;
+            r++;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+int srbm_gait_get_line_search_result(srbm_gait* g, int* imin, double* costs) {
+    if (!g) return fail("srbm_gait_get_line_search_result: bad arguments");
+    const size_t B = g->h->batch;
+    return fetch(g->h, {{imin, g->imin, sizeof(int) * B}, {costs, g->costs, sizeof(double) * SRBM_LS_SIZE * B}});
 }
 // diagnostic / test hook: the batch of line-search candidates (LS_SIZE per instance, candidate c of instance b at index b * LS_SIZE + c), owned by
 // the gait handle -- for the read-back entries (status, sizes, srbm_export_qp) only

@@ -155,6 +155,7 @@ int srbm_plant_set_state(srbm_batch*, double*)
 int srbm_plant_get_state(srbm_batch*, double*)
 int srbm_plant_set_push(srbm_batch*, double*, double*)
 int srbm_closed_loop_advance(srbm_batch*, int, int, int, int)
+int srbm_plant_advance(srbm_batch*, int, int, int, double*, double*, double*)
 int srbm_synchronize(srbm_batch*)
 void* srbm_stream(srbm_batch*)
 int srbm_step_log_record_doubles()
@@ -194,6 +195,8 @@ int srbm_gait_set_step(srbm_gait*, double*)
 int srbm_gait_get_step(srbm_gait*, double*)
 int srbm_gait_line_search(srbm_gait*, double*, double*, double*, int*, double*)
 int srbm_gait_rti_advance(srbm_gait*, int, int, int)
+int srbm_gait_closed_loop_advance(srbm_gait*, int, int, int, int, int)
+int srbm_gait_get_line_search_result(srbm_gait*, int*, double*)
 int srbm_gait_get_candidate_status(srbm_gait*, int*, int*)
 srbm_batch* srbm_gait_debug_candidates(srbm_gait*)
 int srbm_set_leg_kinematics(srbm_batch*, srbm_leg_kinematics*)
@@ -309,7 +312,8 @@ SOLVE_TYPE_NAMES = {0: 'Solved', 1: 'Solved Inacc', 2: 'Max Iter', 3: 'P - Infea
                     6: 'D - Infeasible Inacc', 7: 'Unsolved'}      # MPC::PrintStatLineToFile, mpc.cpp:944-972
 
 
-# One record of the step log (include/srbm_rti.h: srbm_step_log_*): field name -> slice of its STEP_LOG_DOUBLES doubles; [58, 64) is reserved
+# One record of the step log (include/srbm_rti.h: srbm_step_log_*): field name -> slice of its STEP_LOG_DOUBLES doubles; [58, 64) is written by
+# srbm_gait_closed_loop_advance alone (gait_rollout.GAIT_LOG_FIELDS) and 0 from every other entry
 STEP_LOG_DOUBLES = 64
 STEP_LOG_FIELDS = {
     'solve_number': slice(0, 1), 'init_time': slice(1, 2), 'status': slice(2, 3), 'err': slice(3, 4), 'solve_flags': slice(4, 5),

@@ -141,6 +141,11 @@ int srbm_plant_set_state(srbm_batch* h, const double* state);
 int srbm_plant_get_state(srbm_batch* h, double* state);
 int srbm_plant_set_push(srbm_batch* h, const double* time, const double* impulse);
 int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int substeps, int advance_time);
+/* The plant half of iteration `index` on its own: integrate from index*dt to (index+1)*dt, apply the push, fill the device input buffers of the
+ * next solve -- and run NO solve.  Bitwise the inputs srbm_closed_loop_advance(h, index, 1, ..) hands to its solve, so a host may drive the loop
+ * itself: srbm_plant_advance, then any entry that takes (state, init_time, ee).  Synchronous; outputs state[batch][13], time[batch] (= the
+ * init_time of the next solve), ee[batch][4][3], any of them may be NULL.  Never logs. */
+int srbm_plant_advance(srbm_batch* h, int index, int substeps, int advance_time, double* state, double* time, double* ee);
 int srbm_synchronize(srbm_batch* h);
 void* srbm_stream(srbm_batch* h);            /* hipStream_t the kernels are launched on */
 
@@ -148,8 +153,10 @@ void* srbm_stream(srbm_batch* h);            /* hipStream_t the kernels are laun
  * A K-step launch leaves only its LAST solve in the read-back entries (status, stats, QP cost, merit, solve flags, plant state, the trajectory).
  * With a log enabled, every solve of srbm_rti_advance, srbm_closed_loop_advance (both launch forms), srbm_rti_advance_unfused and
  * srbm_get_real_time_update[_dev] also writes one record per instance, with no host round trip: the multi-step kernels write it after the update
- * phase of each step, the one-step entries through one small kernel behind their four.  srbm_create_initial_run, the srbm_gait_* entries and the
- * line-search candidates never log.  Logging changes no result (tests/test_gpu_step_log.py: bitwise).
+ * phase of each step, the one-step entries through one small kernel behind their four.  srbm_gait_closed_loop_advance writes one record per run
+ * and instance (fields 58..63 are its own, see there).  srbm_create_initial_run, srbm_plant_advance, every other srbm_gait_* entry
+ * (srbm_gait_rti_advance included) and the line-search candidates never log.  Logging changes no result (tests/test_gpu_step_log.py,
+ * tests/test_gpu_gait_closed_loop.py: bitwise).
  * The log is log[slot][batch][SRBM_STEP_LOG_DOUBLES]; a call of `steps` steps fills the slots [cursor, cursor + steps) and moves the cursor.  One
  * record, integers stored as doubles:
  *     index     content                                                                   the one-step read-back it equals
@@ -165,7 +172,13 @@ void* srbm_stream(srbm_batch* h);            /* hipStream_t the kernels are laun
  *     30..41    the foot locations handed to the solve [4][3]
  *     42..53    Trajectory::GetForce(ee, init_time) of the NEW trajectory [4][3]          srbm_eval_trajectory at init_time
  *     54..57    the contact flags of the new trajectory at init_time [4]                  srbm_eval_trajectory at init_time
- *     58..63    reserved, 0
+ *     58..63    0 from every entry but srbm_gait_closed_loop_advance, which writes:
+ *     58        kind of the run for this instance: 0 plain, 1 gradient and LP, 2 line search
+ *               with a ready gradient (an instance that was not ready at a line-search run
+ *               took the plain update and gets 0)
+ *     59        the ready flag after the run
+ *     60, 61    lp_status, pred_red (kind 1 only, else 0)                                 srbm_gait_get_lp_result
+ *     62, 63    imin, the winner's cost / n (kind 2 only, else 0)                         srbm_gait_get_line_search_result
  * The merit is not a field: it is cost + 5000 * defect (fields 8 and 9) formed on the host, as srbm_get_merit forms it.  The evaluation behind
  * 42..57 reads the instance only (its error bits stay as the solve left them); a foot whose spline lookup fails gets NaN forces and flag -1.
  * srbm_step_log_enable allocates max_steps x batch records and sets the cursor to 0; max_steps = 0 disables logging and frees the buffer.  A call
@@ -293,6 +306,26 @@ int srbm_gait_line_search(srbm_gait* g, const double* state, const double* init_
  *   otherwise                                 : MPC::GetRealTimeUpdate
  * Asynchronous on the batch's stream; srbm_synchronize(h) to wait. */
 int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq);
+/* The same loop CLOSED over the plant of srbm_closed_loop_advance (controllers/mpc_controller.cpp:286-399: measured state in, one of the three
+ * branches, out): for run r = first_run_num + i, r >= 1, t = r*dt
+ *   plant:      exactly iteration r - 1 of srbm_closed_loop_advance -- integrate from t - dt to t under the current trajectory (substeps,
+ *               advance_time as there), the instance's push if t - dt < push_time <= t, then (plant state, t, foot locations of the current
+ *               trajectory at t) to the solve;
+ *   controller: exactly the branch of srbm_gait_rti_advance on r -- r % freq == 0: line search for the instances whose gradient is ready, the
+ *               plain update (zero-step candidates) for the others; (r + 1) % freq == 0: an RTI taken to the gap criterion whatever the batch's step
+ *               rule says, then gradient and LP, ready := valid && lp_status == 0; otherwise a plain RTI, ready := 0.
+ * MPC::AdjustForCurrentContacts (mpc_controller.cpp:312) is left out, as in srbm_closed_loop_advance: the plant has no contact model, its
+ * "measured" contacts would be the plan's own.  A maximal stretch of plain runs is one multi-step plant launch (both launch forms of
+ * srbm_rti_advance); with gait_opt_freq larger than the last run number the entry is bitwise srbm_closed_loop_advance(h, first_run_num - 1, steps, ..).
+ * Refused, with nothing launched: no plant state set, first_run_num < 1, steps < 0, gait_opt_freq <= 0, substeps < 1, a step log without room
+ * for `steps` records.  With a log enabled every run writes one record per instance: fields 0..57 as in the table above -- on a line-search run of
+ * a ready instance 0 and 2..16 are still those of the instance's own last solve (only the winner's TRAJECTORY is installed, as
+ * MPC::SetWarmStartTrajectory does), 1 is t, 17..41 the inputs from the plant, 42..57 evaluated on the installed trajectory -- and 58..63 the
+ * outcome of the gait step.  Asynchronous on the batch's stream; srbm_synchronize(h) to wait. */
+int srbm_gait_closed_loop_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq, int substeps, int advance_time);
+/* imin[batch], costs[batch][10] of the LAST line search, whichever entry ran it (srbm_gait_line_search returns them itself; the advance entries
+ * keep them on the device).  imin = -1 for an instance that was not ready and took the plain update.  Either pointer may be NULL. */
+int srbm_gait_get_line_search_result(srbm_gait* g, int* imin, double* costs);
 /* solver status / error bits of the candidates of the last line search: status[batch*10], err[batch*10] */
 int srbm_gait_get_candidate_status(srbm_gait* g, int* status, int* err);
 /* test hook: the candidate batch of the last line search (borrowed: never destroy it), candidate c of instance b at b * 10 + c; for the

@@ -19,3 +19,5 @@ workloads = _load('srbm_workloads', 'workloads.py')
 workloads.REFERENCE_SOLVER_SETTINGS = host.REFERENCE_SOLVER_SETTINGS       # one definition (host.py), reachable from both
 sys.modules[__name__ + '.workloads'] = workloads          # `from srbm_loader.workloads import ...`
 sys.modules[__name__ + '.host'] = host
+gait_rollout = _load('srbm_gait_rollout', 'gait_rollout.py')
+sys.modules[__name__ + '.gait_rollout'] = gait_rollout

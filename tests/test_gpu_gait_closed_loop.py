@@ -1,0 +1,283 @@
+"""The controller loop with the gait step, closed over the plant and logged (include/srbm_rti.h: srbm_gait_closed_loop_advance, srbm_plant_advance,
+srbm_gait_get_line_search_result; csrc/srbm_gait_rollout.hiph), through bilevel-gait-gen_amd/gait_rollout.py.  All batches run in the mode (0, 0).
+
+    1  plain runs only (gait_opt_freq beyond the last run): bitwise srbm_closed_loop_advance, records included, fields 58..63 zero;
+    2  one call of 11 runs, 11 calls of one run and the same protocol driven from the host through public entries end bitwise equal; the records of
+       the first two are the same bytes and equal the read-backs after every one-run call; logging changes no result;
+    3  against the CPU restatement's own closed loop, re-synchronised before every run, through two line searches;
+    4  a batch larger than the chip: the plain stretch runs on the step queues, bitwise the results without them;
+    5  the refusals leave the batch untouched."""
+import numpy as np
+import pytest
+
+from gait_rollout_kit import GRADIENT, LINE_SEARCH, PLAIN, RestatementLoop
+from gpu_kit import REL_TOL, relerr, same_bytes
+from oracle_py import load_config
+from srbm_loader import gait_rollout, host
+from srbm_loader.workloads import EE_NOMINAL, config_b_instance, instances
+
+pytestmark = pytest.mark.gpu
+MODE = (0.0, 0.0)
+SUB = 4
+F = host.STEP_LOG_FIELDS
+GF = gait_rollout.GAIT_LOG_FIELDS
+
+
+def rollout(g, log=0):
+    """the gait optimiser and the rollout of a batch whose plant is set; log: room for that many runs"""
+    if log:
+        g.step_log_enable(log)
+    gait = host.BatchGaitOptimizer(g)
+    return gait, gait_rollout.GaitRollout(g, gait)
+
+
+def end_state(g, gait=None):
+    st, err = g.status()
+    out = dict(plant=g.plant_state(), states=g.trajectory_states(), x=g.qp_solution(), status=st, err=err,
+               trajectory=np.frombuffer(bytes(g.get_trajectory()), np.uint8))           # (the knot tables among it)
+    if gait is not None:
+        out['contact_times'], out['counts'] = gait.contact_times()
+    return out
+
+
+def assert_same(a, b, what, keys=None):
+    for k in keys or a:
+        same_bytes(a[k], b[k], '%s: %s' % (what, k))
+
+
+@pytest.mark.parametrize('advance_time', [False, True], ids=['time_held', 'time_advanced'])
+def test_plain_runs_are_bitwise_the_closed_loop_advance(advance_time):
+    """a1_configuration, 8 instances with the pushes of test_closed_loop_fused_steps_equal_single_steps_and_push_distribution, 6 runs from run 1
+    with gait_opt_freq 1000 against srbm_closed_loop_advance(0, 6, ..) on a twin batch"""
+    cfg = load_config()
+    B, K = 8, 6
+    states, ees = instances(cfg, config_b_instance, B)
+    rng = np.random.default_rng(5)
+    pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    base.plant_set_state(states); base.plant_set_push(pt, imp)
+    twin, g = base.clone(), base.clone()
+    twin.step_log_enable(K)
+    twin.closed_loop_advance(0, K, SUB, advance_time); twin.synchronize()
+    gait, roll = rollout(g, log=K)
+    roll.advance(1, K, 1000, SUB, advance_time); g.synchronize()
+    assert g.step_log_count() == K and g.debug_launch_info() == twin.debug_launch_info()
+    assert_same(end_state(g), end_state(twin), 'plain runs against srbm_closed_loop_advance')
+    rec = g.step_log()
+    same_bytes(rec, twin.step_log(), 'the six records')
+    assert rec.shape == (K, B, 64) and not rec[:, :, 58:].any()
+    assert np.abs(g.plant_state()[:, 3:6] - states[:, 3:6]).max() > 0.5                          # (the pushes arrived)
+    for b in (g, twin, base):
+        b.close()
+
+
+# config_b instances 0..2 under these pushes: the CPU restatement's own closed loop has a valid gradient and a solved LP at runs 4 and 9 for each of
+# them (checked with tests/gait_rollout_kit.py before they were chosen; instance 2 is never pushed)
+PUSH_TIME_3 = np.array([0.12, 0.07, 1e9])
+IMPULSE_3 = np.array([[2.5, -1.0, 0.3, 0.05, -0.1, 0.2], [-1.5, 2.0, 0.0, 0.0, 0.1, -0.1], [9, 9, 9, 9, 9, 9]], float)
+
+
+def test_one_call_single_calls_and_the_host_driven_loop_agree_bitwise():
+    cfg = load_config()
+    B, FREQ, RUNS = 3, 5, 11
+    dt = cfg['integrator_dt']
+    states, ees = instances(cfg, config_b_instance, B)
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    base.plant_set_state(states); base.plant_set_push(PUSH_TIME_3, IMPULSE_3)
+    ga, gb, gc, gd = (base.clone() for _ in range(4))
+
+    # (a) one call of 11 runs
+    gait_a, roll_a = rollout(ga, log=RUNS)
+    roll_a.advance(1, RUNS, FREQ, SUB, True); ga.synchronize()
+    rec_a = ga.step_log()
+    assert rec_a.shape == (RUNS, B, 64)
+
+    # (b) 11 calls of one run: after every call the record equals the read-backs
+    gait_b, roll_b = rollout(gb, log=RUNS)
+    for r in range(1, RUNS + 1):
+        roll_b.advance(r, 1, FREQ, SUB, True); gb.synchronize()
+        assert gb.step_log_count() == r
+        rec = gb.step_log(r - 1, 1)[0]
+        t = (r - 1) * dt + dt
+        assert np.all(rec[:, 1] == t)
+        st, err = gb.status()
+        same_bytes(rec[:, 2], st.astype(float), 'run %d: status' % r); same_bytes(rec[:, 3], err.astype(float), 'run %d: error bits' % r)
+        assert not err.any(), (r, err)
+        same_bytes(rec[:, F['stats']], gb.stats(), 'run %d: stats' % r)
+        same_bytes(rec[:, 15], gb.qp_cost(), 'run %d: QP cost' % r)
+        same_bytes(rec[:, F['state']], gb.plant_state(), 'run %d: plant state' % r)
+        force, _, contact = gb.eval_trajectory(t)
+        same_bytes(rec[:, F['force']], force.reshape(B, 12), 'run %d: forces of the installed trajectory' % r)
+        same_bytes(rec[:, F['in_contact']], contact.astype(float), 'run %d: contact flags' % r)
+        kind = GRADIENT if (r + 1) % FREQ == 0 else LINE_SEARCH if r % FREQ == 0 else PLAIN
+        expect = np.zeros((B, 6))
+        if kind == GRADIENT:
+            lp_status, pred_red = gait_b.lp_result()
+            valid = gait_b.gradient()[1]
+            expect[:, 0], expect[:, 1], expect[:, 2], expect[:, 3] = 1, (valid == 1) & (lp_status == 0), lp_status, pred_red
+            # the public line search of (c) cannot express "this instance was not ready": every instance must be
+            assert np.all(rec[:, GF['ready']] == 1), (r, rec[:, 58:])
+        elif kind == LINE_SEARCH:
+            imin, costs = roll_b.line_search_result()
+            assert np.all((imin >= 0) & (imin < 10)), (r, imin)
+            expect[:, 0], expect[:, 4], expect[:, 5] = 2, imin, costs[np.arange(B), imin]
+        same_bytes(rec[:, 58:], expect, 'run %d: fields 58..63' % r)
+        for b in range(B):
+            assert gait_rollout.gait_fields_from_log(rec[b])['kind'] == kind
+    same_bytes(gb.step_log(), rec_a, 'records of 11 one-run calls against one call of 11 runs')
+    assert [int(k) for k in rec_a[:, 0, GF['kind']]] == [0, 0, 0, 1, 2, 0, 0, 0, 1, 2, 0]
+
+    # (c) the same protocol from the host, through public entries
+    gait_c, roll_c = rollout(gc)
+    for r in range(1, RUNS + 1):
+        state, time, ee = roll_c.plant_advance(r - 1, SUB, True)
+        same_bytes(state, rec_a[r - 1][:, F['state']], 'run %d: srbm_plant_advance state against the record' % r)
+        same_bytes(ee.reshape(B, 12), rec_a[r - 1][:, F['ee']], 'run %d: srbm_plant_advance foot locations against the record' % r)
+        same_bytes(time, rec_a[r - 1][:, 1], 'run %d: srbm_plant_advance time against the record' % r)
+        if r % FREQ == 0:
+            imin, costs = gait_c.line_search(state, time, ee)
+            same_bytes(imin.astype(float), rec_a[r - 1][:, GF['imin']], 'run %d: imin of the public line search against the record' % r)
+        elif (r + 1) % FREQ == 0:
+            gc.get_real_time_update(state, time, ee)
+            gait_c.compute_gradient()
+            gait_c.optimize_contact_times(time)
+        else:
+            gc.get_real_time_update(state, time, ee)
+    gc.synchronize()
+    assert gc.step_log_count() == 0
+
+    # (d) no log
+    gait_d, roll_d = rollout(gd)
+    roll_d.advance(1, RUNS, FREQ, SUB, True); gd.synchronize()
+
+    ea = end_state(ga, gait_a)
+    assert_same(end_state(gb, gait_b), ea, '11 one-run calls against one call')
+    assert_same(end_state(gc, gait_c), ea, 'the host-driven loop against one call', keys=('plant', 'states', 'trajectory', 'contact_times', 'counts'))
+    assert_same(end_state(gd, gait_d), ea, 'without a log against with one')
+    same_bytes(np.concatenate(roll_d.line_search_result(), axis=None), np.concatenate(roll_a.line_search_result(), axis=None), 'last line search')
+    # the pushes are in the plant, and the gait step moved the schedule of the instances away from the nominal one
+    assert np.abs(ea['plant'][0, 3:6] - ea['plant'][2, 3:6]).max() > 0.5
+    for b in (ga, gb, gc, gd, base):
+        b.close()
+
+
+PUSH = np.array([1.5, -1.0, 0.2, 0.03, -0.05, 0.1])
+
+
+@pytest.mark.parametrize('cfgname,push_time', [('a1_gait_opt_config', 0.05), ('a1_configuration', 0.12)])
+def test_closed_loop_with_gait_step_against_the_restatement_resynchronised(cfgname, push_time):
+    """The closed-loop twin of test_controller_loop_with_gait_step with resync=True: two identical instances, 11 runs, a push.  Before every run the
+    device is given the restatement's trajectory and plant state, after a gradient run its LP step (the LP itself is compared in
+    test_contact_time_lp_matches_oracle).  Checked on the CPU for exactly these inputs: the restatement has a valid gradient and a solved LP at runs
+    4 and 9 in both configurations, and at all four line searches its two cheapest candidates are more than 1e-4 apart (the closest: 1.1e-3), so
+    the argmin is compared every time."""
+    FREQ, RUNS = 5, 11
+    cfg = load_config(cfgname)
+    s0 = np.array(cfg['srb_init'], float)
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=MODE)
+    g.plant_set_state(s0); g.plant_set_push(push_time, PUSH)
+    gait, roll = rollout(g, log=RUNS)
+    loop = RestatementLoop(cfg, s0, EE_NOMINAL, FREQ, SUB, 1, push_time, PUSH)
+    n_ls = n_argmin = 0
+    for r in range(1, RUNS + 1):
+        g.set_warm_start_trajectory([loop.o.trajectory_record(host)] * 2)
+        g.plant_set_state(loop.x)
+        out = loop.run()
+        roll.advance(r, 1, FREQ, SUB, True); g.synchronize()
+        if out['step'] is not None:
+            nv = int(gait.contact_times()[1][0].sum())
+            gait.set_step(out['step'][:nv])
+        st, err = g.status()
+        assert not err.any(), (r, err)
+        plant, tr = g.plant_state(), g.trajectory_states()
+        e_plant, e_tr = relerr(plant[0], out['plant']), relerr(tr[0], loop.o.states())
+        print('%s run %2d kind %d: plant %.1e states %.1e' % (cfgname, r, out['kind'], e_plant, e_tr))
+        assert np.array_equal(plant[0], plant[1]) and np.array_equal(tr[0], tr[1]), r
+        assert e_plant <= 1e-9, (r, e_plant)             # identical records in: the project's own figure for one plant step is 1e-12
+        assert e_tr < REL_TOL, (r, e_tr)
+        kg = g.knots(0)
+        same_bytes(np.frombuffer(bytes(g.get_trajectory(0, 1)), np.uint8), np.frombuffer(bytes(g.get_trajectory(1, 1)), np.uint8), 'run %d: the two instances' % r)
+        for e in range(4):
+            ko = loop.o.knots(e)
+            assert kg['nk'][e] == ko['K'] and np.array_equal(kg['times'][e, :ko['K']], ko['times']), (r, e)
+        rec = g.step_log(r - 1, 1)[0]
+        same_bytes(rec[0], rec[1], 'run %d: the records of the two instances' % r)
+        fields = gait_rollout.gait_fields_from_log(rec[0])
+        assert fields['kind'] == out['kind'], (r, fields, out['kind'])
+        if out['kind'] == GRADIENT:
+            assert fields['ready'] == int(out['ready']) == 1 and fields['lp_status'] == 0, (r, fields)
+        if out['kind'] == LINE_SEARCH:
+            n_ls += 1
+            imin, costs = roll.line_search_result()
+            assert imin[0] == imin[1] == fields['imin']
+            srt = np.sort(out['costs'])
+            print('   line search: device imin %d, restatement %d; its two cheapest candidates %.3e apart (relative)' %
+                  (imin[0], out['imin'], (srt[1] - srt[0]) / max(1.0, abs(srt[0]))))
+            if srt[1] - srt[0] > 1e-4 * max(1.0, abs(srt[0])):
+                n_argmin += 1
+                assert imin[0] == out['imin'], (r, imin[0], out['imin'], costs[0], out['costs'])
+    assert n_ls == 2 and n_argmin == 2, (n_ls, n_argmin)
+    g.close()
+
+
+def test_a_batch_larger_than_the_chip_takes_the_step_queues_in_its_plain_stretch(monkeypatch):
+    """CU count + 4 instances, N = 20, runs 1..5 with gait_opt_freq 5: the three plain runs are one queued launch; against a batch created with the
+    step queues switched off (the switch is read when a batch is created)"""
+    cfg = load_config()
+    probe = host.BatchMPC(cfg, 1)
+    n_cu = probe.debug_launch_info()['n_cu']
+    probe.close()
+    B = n_cu + 4
+    states, ees = instances(cfg, config_b_instance, B)
+    pt = np.full(B, 1e9); pt[::7] = 0.07
+    imp = np.zeros((B, 6)); imp[::7, 0] = 1.5; imp[::7, 1] = -1.0
+    res = {}
+    for no_queue in (False, True):
+        if no_queue:
+            monkeypatch.setenv('SRBM_NO_STEP_QUEUE', '1')
+        else:
+            monkeypatch.delenv('SRBM_NO_STEP_QUEUE', raising=False)
+        g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+        g.plant_set_state(states); g.plant_set_push(pt, imp)
+        gait, roll = rollout(g, log=5)
+        roll.advance(1, 5, 5, SUB, True); g.synchronize()
+        info = g.debug_launch_info()
+        assert info == dict(n_cu=n_cu, kernel='srbm_rti_fused' if no_queue else 'srbm_rti_queued', steps=3, queued=not no_queue), info
+        res[no_queue] = dict(end_state(g, gait), records=g.step_log())
+        assert not res[no_queue]['err'].any()
+        g.close()
+    assert_same(res[False], res[True], 'step queues against one workgroup per instance')
+    kinds = res[False]['records'][:, :, GF['kind']]
+    assert np.all(kinds[:4] == np.array([0, 0, 0, 1])[:, None]) and set(np.unique(kinds[4])) <= {0.0, 2.0} and (kinds[4] == 2).any()
+
+
+def test_refusals_leave_the_batch_untouched():
+    cfg = load_config()
+    B = 2
+    states, ees = instances(cfg, config_b_instance, B)
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    gait, roll = rollout(g, log=3)
+    traj = bytes(g.get_trajectory())
+    with pytest.raises(RuntimeError, match='plant state has not been set'):
+        roll.advance(1, 1, 5, SUB, True)
+    with pytest.raises(RuntimeError, match='plant state has not been set'):
+        roll.plant_advance(0, SUB, True)
+    assert bytes(g.get_trajectory()) == traj and g.step_log_count() == 0
+    g.plant_set_state(states); g.plant_set_push(0.01, PUSH)
+    plant = g.plant_state()
+    for args, why in (((0, 1, 5, SUB, True), 'first_run_num'), ((1, 1, 5, 0, True), 'substeps'), ((1, 1, 0, SUB, True), 'gait_opt_freq'),
+                      ((1, -1, 5, SUB, True), 'steps'), ((1, 4, 5, SUB, True), 'room for 3 more steps')):
+        with pytest.raises(RuntimeError, match=why):
+            roll.advance(*args)
+        g.synchronize()
+        same_bytes(g.plant_state(), plant, 'plant state after the refusal (%s)' % why)
+        assert bytes(g.get_trajectory()) == traj and g.step_log_count() == 0, why
+    with pytest.raises(RuntimeError, match='bad arguments'):
+        roll.plant_advance(0, 0, True)
+    same_bytes(g.plant_state(), plant, 'plant state after the refused plant step')
+    # and what fits is accepted: three runs into the three slots
+    roll.advance(1, 3, 5, SUB, True); g.synchronize()
+    assert g.step_log_count() == 3 and not g.status()[1].any()
+    with pytest.raises(RuntimeError, match='room for 0 more steps'):
+        roll.advance(4, 1, 5, SUB, True)
+    g.close()
