@@ -341,6 +341,23 @@ int srbm_debug_hmatvec(int n, int count, const double* H_packed, const double* x
     HIPCHK(tmp.alloc(&dH, bytes)); HIPCHK(tmp.alloc(&dx, vb)); HIPCHK(tmp.alloc(&dy, vb));
     return run_dense_hook(srbm_k_debug_hmatvec, count, DBG_HMATVEC_LDS_BYTES, {{dH, H_packed, bytes}, {dx, xin, vb}}, {{y, dy, vb}}, n, dH, dx, dy);
 }
+/* unit-test hook of the IPM's staging of H (k3_load_h_o) and of the LDS map it publishes: `count` packed n x n matrices H, each into the H of a work
+   record of its own, one workgroup of the IPM's launch shape each.  out[count][np + guard] <- the matrix of the solve and the `guard` (<= 64) doubles
+   behind it after the staging, all of them set to the bit pattern 0xDEADBEEFCAFEF00D before it.  map5 (optional) [count][5] <- what an out-of-line phase reads
+   of the map of a solve (N, n, wc): wc, rows in the tail of the matrix window, 1 if all rows are in LDS, offset of the tail rows, offset of the
+   rows behind the map (doubles into the LDS) */
+int srbm_debug_h_stage(int n, int count, const double* H_packed, double* out, int guard, int N, int wc, int* map5) {
+    if (n <= 0 || n > SRBM_NUMAX || count <= 0 || !H_packed || !out || guard < 0 || guard > 64) return fail("bad arguments");
+    if (map5 && (N < 4 || N > SRBM_NMAX || wc <= 0 || wc > K3_WCMAX)) return fail("bad arguments");
+    const size_t np = (size_t)n * (n + 1) / 2, ob = (np + guard) * count * sizeof(double), mb = sizeof(int) * 5 * count;
+    SrbmWork* dW = nullptr; double* dout = nullptr; int* dmap = nullptr;
+    DevTemps tmp;
+    HIPCHK(tmp.alloc(&dW, sizeof(SrbmWork) * count)); HIPCHK(tmp.alloc(&dout, ob));
+    if (map5) HIPCHK(tmp.alloc(&dmap, mb));
+    for (int b = 0; b < count; b++) HIPCHK(hipMemcpy(dW[b].H, H_packed + b * np, np * sizeof(double), hipMemcpyHostToDevice));
+    return run_dense_hook(srbm_k_debug_h_stage, count, K3_LDS_LAUNCH_BYTES, {}, {{out, dout, ob}, {map5, dmap, mb}}, n, dW, dout, guard, N, wc,
+                          (int)(K3_LDS_LAUNCH_BYTES / sizeof(double)), dmap);
+}
 /* host only: where the IPM of this library puts the 2 (N - 3) compact dense state rows of width wc at n_u = nu (k3_sig_placement, the arithmetic of
    its LDS map): out3 = rows in the tail of the packed-matrix window, rows behind the LDS map, 1 if all are in LDS (0: read from L2) */
 int srbm_debug_dense_row_placement(int N, int nu, int wc, int* out3) {

@@ -14,7 +14,14 @@
 /* The dynamic LDS of the workgroup, under the only name the library gives it.  The compiler treats two such declarations as two objects that
    cannot alias, though both are the same bytes.  Every kernel lays its own views over it (K3Smem, the K1/K2/K4 working sets of the fused kernels
    through srbm_lds_view, the offsets of the dense helpers); a change from one view to another is preceded by a workgroup barrier. */
-extern __shared__ double srbm_lds[];
+/* (the diagnostic build has 8 bytes of static LDS in front of it, the clock of its stamps: there the 16-byte units of the IPM's LDS-DMA staging of H
+   need the alignment said; without static LDS the dynamic LDS begins at address 0) */
+#ifdef SRBM_PROFILE
+#define SRBM_LDS_ALIGN __attribute__((aligned(16)))
+#else
+#define SRBM_LDS_ALIGN
+#endif
+extern __shared__ SRBM_LDS_ALIGN double srbm_lds[];
 
 #define SRBM_NEE 4
 /* Where the packed normal matrix of the IPM lives: LDS (standard build: one workgroup of 512 threads per CU) or the work record in global
