@@ -18,6 +18,7 @@
 #include "srbm_gait_rollout.hiph"
 #include "srbm_ik.hiph"
 #include "srbm_wbc.hiph"
+#include "srbm_tick.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
 #include "../../include/srbm_rti.h"
@@ -82,6 +83,9 @@ struct srbm_batch {
     size_t stage_bytes = 0;
     double* d_log = nullptr;         // step log [log_cap][batch][SRBM_STEP_LOG_DOUBLES] (srbm_steplog.hiph), nullptr: logging off
     int log_cap = 0, log_used = 0;   // slots allocated; the cursor: slots written by the launches queued so far
+    // control tick (srbm_control_tick, srbm_tick.hiph): MPCController's member state for the batch, allocated by srbm_control_tick_reset
+    double* d_tick_q = nullptr;              // q_des_ [batch][19]
+    SrbmTickRec* d_tick_rec = nullptr;       // the targets of the tick under way [batch], between its two kernels
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -393,10 +397,18 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_state); (void)hipFree(h->d_time); (void)hipFree(h->d_ee);
     (void)hipFree(h->d_plant); (void)hipFree(h->d_push_time); (void)hipFree(h->d_push_impulse);
     (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage); (void)hipFree(h->d_log);
+    (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
+}
+// the control tick's buffers (srbm_control_tick_reset, srbm_batch_clone)
+static int tick_alloc(srbm_batch* h) {
+    const size_t B = h->batch;
+    if (!h->d_tick_q) HIPCHK(hipMalloc(&h->d_tick_q, sizeof(double) * 19 * B));
+    if (!h->d_tick_rec) HIPCHK(hipMalloc(&h->d_tick_rec, sizeof(SrbmTickRec) * B));
+    return 0;
 }
 static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     const size_t B = h->batch;
@@ -531,6 +543,8 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
              cp(h->d_push_time, src->d_push_time, sizeof(double) * B) && cp(h->d_push_impulse, src->d_push_impulse, sizeof(double) * 6 * B);
     }
     if (ok && src->d_wbc) ok = hipMalloc(&h->d_wbc, sizeof(SrbmWbcParams)) == hipSuccess && cp(h->d_wbc, src->d_wbc, sizeof(SrbmWbcParams));      // (a clone carries the complete state)
+    // (the control tick's q_des_ goes along)
+    if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -1880,6 +1894,61 @@ int srbm_qp_control_dev(srbm_batch* h, const double* q_dev, const double* v_dev,
     hipLaunchKernelGGL(srbm_k_qp_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, q_dev, v_dev, contact_dev, q_des_dev, v_des_dev,
                        force_des_dev, control_dev, qp_sol_dev, status_dev, static_cast<double*>(nullptr));
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---------------- the control tick as one entry (srbm_tick.hiph) ----------------
+// what both entries need, asked before anything is staged, copied or launched
+static int tick_usable(srbm_batch* h) {
+    if (need_legs(h)) return -1;
+    if (!h->d_wbc) return fail("the whole-body model has not been set (srbm_set_wbc_model)");
+    if (!h->d_tick_q) return fail("srbm_control_tick: q_des has not been set (srbm_control_tick_reset: the IK guess of the first tick)");
+    return 0;
+}
+int srbm_control_tick_reset(srbm_batch* h, const double* q_des) {
+    if (!h || !q_des) return fail("srbm_control_tick_reset: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (tick_alloc(h)) return -1;
+    HIPCHK(hipMemcpyAsync(h->d_tick_q, q_des, sizeof(double) * 19 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_control_tick_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* time_dev, double* control_dev, double* qp_sol_dev, int* status_dev,
+                          double* q_des_dev, double* v_des_dev, int* contact_dev, double* state_dev, double* ee_dev) {
+    if (!h || !q_dev || !v_dev || !time_dev || !control_dev || !qp_sol_dev || !status_dev) return fail("srbm_control_tick: bad arguments");
+    if (tick_usable(h) || use_batch(h)) return -1;
+    hipLaunchKernelGGL(srbm_k_tick_targets, dim3(h->batch), dim3(SRBM_TT_THREADS), 0, h->stream, h->dp, h->insts, time_dev, h->d_tick_q, h->d_tick_rec);
+    const SrbmTickIO io{q_dev, v_dev, time_dev, control_dev, qp_sol_dev, status_dev, q_des_dev, v_des_dev, contact_dev, state_dev, ee_dev};
+    hipLaunchKernelGGL(srbm_k_tick_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, h->d_tick_rec, h->d_tick_q, io);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_control_tick(srbm_batch* h, const double* q, const double* v, const double* time, double* control, double* qp_sol, int* status, double* q_des,
+                      double* v_des, int* contact, double* state, double* ee) {
+    if (!h || !q || !v || !time || !control || !qp_sol || !status) return fail("srbm_control_tick: bad arguments");
+    if (tick_usable(h)) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = h->batch;
+    Carve c;                                          // in: q, v, time; out: control .. ee
+    const auto iq = c.add<double>(19 * B), iv = c.add<double>(18 * B), it = c.add<double>(B);
+    const auto oc = c.add<double>(36 * B), os = c.add<double>(WBC_NMAX * B), oq = c.add<double>(19 * B), ov = c.add<double>(18 * B), ox = c.add<double>(13 * B),
+               oe = c.add<double>(12 * B);
+    const auto ost = c.add<int>(2 * B), ocon = c.add<int>(4 * B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(iq), q, iq.bytes());
+    memcpy(c.host(iv), v, iv.bytes());
+    memcpy(c.host(it), time, it.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(iq), c.host(iq), Carve::span(iq, it), hipMemcpyHostToDevice, h->stream));
+    if (srbm_control_tick_dev(h, c.dev(iq), c.dev(iv), c.dev(it), c.dev(oc), c.dev(os), c.dev(ost), c.dev(oq), c.dev(ov), c.dev(ocon), c.dev(ox), c.dev(oe))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(oc), c.dev(oc), Carve::span(oc, ocon), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(control, c.host(oc), oc.bytes());
+    memcpy(qp_sol, c.host(os), os.bytes());
+    memcpy(status, c.host(ost), ost.bytes());
+    if (q_des) memcpy(q_des, c.host(oq), oq.bytes());
+    if (v_des) memcpy(v_des, c.host(ov), ov.bytes());
+    if (contact) memcpy(contact, c.host(ocon), ocon.bytes());
+    if (state) memcpy(state, c.host(ox), ox.bytes());
+    if (ee) memcpy(ee, c.host(oe), oe.bytes());
     return 0;
 }
 

@@ -207,6 +207,9 @@ int srbm_get_targets_from_traj_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*)
 int srbm_set_wbc_model(srbm_batch*, srbm_wbc_model*)
 int srbm_qp_control(srbm_batch*, double*, double*, int*, double*, double*, double*, double*, double*, int*, double*)
 int srbm_qp_control_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_control_tick_reset(srbm_batch*, double*)
+int srbm_control_tick(srbm_batch*, double*, double*, double*, double*, double*, int*, double*, double*, int*, double*, double*)
+int srbm_control_tick_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

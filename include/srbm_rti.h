@@ -380,6 +380,30 @@ int srbm_qp_control(srbm_batch* h, const double* q, const double* v, const int* 
 int srbm_qp_control_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const int* contact_dev, const double* q_des_dev, const double* v_des_dev,
                         const double* force_des_dev, double* control_dev, double* qp_sol_dev, int* status_dev);
 
+/* ---- the control tick as ONE entry: MPCController::ComputeControlAction (controllers/mpc_controller.cpp:120-227) for every instance, with the
+ * controller's member state q_des_ / v_des_ held by the batch.  = ReconstructState (:229-271) and GetEndEffectorLocations of the measured (q, v),
+ * GetTargetsFromTraj, Trajectory::GetDesiredContacts(time), force_target_ stacked from GetForce (:181-188), QPControl::ComputeControlAction:
+ * bit for bit what srbm_get_targets_from_traj -> srbm_eval_trajectory -> (stacking by the caller) -> srbm_qp_control give.
+ * MEASURED CONTACTS ARE NOT AN ARGUMENT: the reference overwrites in_contact_ with the trajectory's (:172-173) and keeps only the contact frames. ---- */
+/* MPCController's q_des_ (mpc_controller.cpp:206, set up in the constructor / InitSolver): q_des[batch][19], the IK guess of the next tick.
+ * Required once before the first tick. */
+int srbm_control_tick_reset(srbm_batch* h, const double* q_des);
+/* q[batch][19], v[batch][18] measured; time[batch].
+ * control[batch][36], qp_sol[batch][30] as srbm_qp_control; status[batch][2] = {targets status 0 / 1 / 2 as srbm_get_targets_from_traj,
+ * QP status | iterations << 8}.  Each of the following may be NULL: q_des[batch][19], v_des[batch][18] (the targets: q_des_, v_des_ after the
+ * tick), contact[batch][4] (Trajectory::GetDesiredContacts(time)), state[batch][13] (ReconstructState(q, v)), ee[batch][4][3]
+ * (GetEndEffectorLocations(q)) -- the last two are what :142-156 publishes to the MPC thread, in the layout srbm_get_real_time_update[_dev] takes.
+ * Targets status 1 (IK not converged): the QP runs on the q_des the IK left, as the chain of the single entries does.
+ * Targets status 2 (the reference throws): zero control action, zero qp_sol, QP status 8, and the batch's q_des of that instance stays as it was.
+ * q_des / v_des / contact are then what the targets step left -- for a time beyond the horizon: the q_des handed in, zero v_des, no contact.
+ * The instance records are only read: lookup errors are NOT added to the error bits of srbm_get_status (srbm_eval_trajectory adds them).
+ * Fails, before anything is staged or launched, without leg kinematics, whole-body model or srbm_control_tick_reset.  A clone carries q_des. */
+int srbm_control_tick(srbm_batch* h, const double* q, const double* v, const double* time, double* control, double* qp_sol, int* status, double* q_des,
+                      double* v_des, int* contact, double* state, double* ee);
+/* ... on device pointers (same shapes, same optional ones): two launches on the batch's stream, no copy, no synchronisation */
+int srbm_control_tick_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* time_dev, double* control_dev, double* qp_sol_dev, int* status_dev,
+                          double* q_des_dev, double* v_des_dev, int* contact_dev, double* state_dev, double* ee_dev);
+
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */
 int srbm_get_sizes(srbm_batch* h, int* sizes);

@@ -1,5 +1,5 @@
 """Imports the modules of bilevel-gait-gen_amd/ (the directory name is not a Python identifier): `host` (ctypes binding of the C-ABI) and
-`workloads` (seeded instance generators of the BASELINE configurations, sharding)."""
+`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout` and `control_tick` (the entries beside host.py)."""
 import importlib.util
 import os
 import sys
@@ -21,3 +21,5 @@ sys.modules[__name__ + '.workloads'] = workloads          # `from srbm_loader.wo
 sys.modules[__name__ + '.host'] = host
 gait_rollout = _load('srbm_gait_rollout', 'gait_rollout.py')
 sys.modules[__name__ + '.gait_rollout'] = gait_rollout
+control_tick = _load('srbm_control_tick', 'control_tick.py')
+sys.modules[__name__ + '.control_tick'] = control_tick
