@@ -59,8 +59,11 @@ struct srbm_batch {
     SrbmInst* insts = nullptr;
     SrbmWork* works = nullptr;
     double *d_state = nullptr, *d_time = nullptr, *d_ee = nullptr;
-    double *d_plant = nullptr, *d_push_time = nullptr, *d_push_impulse = nullptr;   // closed-loop harness (srbm_plant.hiph)
+    double *d_plant = nullptr, *d_push = nullptr;   // closed-loop harness (srbm_plant.hiph): states [batch][13], pushes [batch][SRBM_PUSH_DOUBLES] {time, impulse[6]}
     bool push_set = false;
+    double* d_dt = nullptr;          // the node step dt [batch]: the `period` of every launch that has no other (SrbmPlantArgs)
+    double* d_period = nullptr;      // MPC period of the closed-loop protocols [batch] (srbm_plant_set_period), allocated at the first set
+    std::vector<double> period;      // its host copy; empty: none set, every instance runs at the node step dt
     hipStream_t stream = nullptr;
     bool owns_stream = true;
     int n_cu = 0;
@@ -395,7 +398,7 @@ static void free_batch(srbm_batch* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->dp); (void)hipFree(h->insts); (void)hipFree(h->works); (void)hipFree(h->queues);
     (void)hipFree(h->d_state); (void)hipFree(h->d_time); (void)hipFree(h->d_ee);
-    (void)hipFree(h->d_plant); (void)hipFree(h->d_push_time); (void)hipFree(h->d_push_impulse);
+    (void)hipFree(h->d_plant); (void)hipFree(h->d_push); (void)hipFree(h->d_period); (void)hipFree(h->d_dt);
     (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage); (void)hipFree(h->d_log);
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
@@ -420,6 +423,8 @@ static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
     HIPCHK(hipMalloc(&h->d_state, sizeof(double) * 13 * B));
     HIPCHK(hipMalloc(&h->d_time, sizeof(double) * B));
     HIPCHK(hipMalloc(&h->d_ee, sizeof(double) * 12 * B));
+    HIPCHK(hipMalloc(&h->d_dt, sizeof(double) * B));
+    { const std::vector<double> dts(B, h->hp.dt); HIPCHK(hipMemcpy(h->d_dt, dts.data(), sizeof(double) * B, hipMemcpyHostToDevice)); }
     // the IPM kernel gets the whole LDS of a CU: what its fixed map leaves over holds the dense state rows (K3Smem::sig_row)
     if (srbm_k3_lds_bytes(h->hp.N) > K3_LDS_LAUNCH_BYTES) return fail("srbm_batch_create: LDS map exceeds 160 KB");
     h->hp.lds_doubles = (int)(K3_LDS_LAUNCH_BYTES / sizeof(double));
@@ -529,7 +534,7 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     HIPCHK(hipStreamSynchronize(src->stream));
     auto* h = new srbm_batch;
     h->batch = src->batch; h->device = src->device; h->hp = src->hp; h->im = src->im; std::memcpy(h->hip_xy, src->hip_xy, sizeof(h->hip_xy));
-    h->push_set = src->push_set; h->last_tol_step = src->last_tol_step;
+    h->push_set = src->push_set; h->last_tol_step = src->last_tol_step; h->period = src->period;
     auto bail = [&]() { free_batch(h); return -1; };
     if (alloc_batch(h, nullptr)) return bail();
     const size_t B = h->batch;
@@ -538,10 +543,10 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
               cp(h->d_state, src->d_state, sizeof(double) * 13 * B) && cp(h->d_time, src->d_time, sizeof(double) * B) &&
               cp(h->d_ee, src->d_ee, sizeof(double) * 12 * B);
     if (ok && src->d_plant) {
-        ok = hipMalloc(&h->d_plant, sizeof(double) * 13 * B) == hipSuccess && hipMalloc(&h->d_push_time, sizeof(double) * B) == hipSuccess &&
-             hipMalloc(&h->d_push_impulse, sizeof(double) * 6 * B) == hipSuccess && cp(h->d_plant, src->d_plant, sizeof(double) * 13 * B) &&
-             cp(h->d_push_time, src->d_push_time, sizeof(double) * B) && cp(h->d_push_impulse, src->d_push_impulse, sizeof(double) * 6 * B);
+        ok = hipMalloc(&h->d_plant, sizeof(double) * 13 * B) == hipSuccess && hipMalloc(&h->d_push, sizeof(double) * SRBM_PUSH_DOUBLES * B) == hipSuccess &&
+             cp(h->d_plant, src->d_plant, sizeof(double) * 13 * B) && cp(h->d_push, src->d_push, sizeof(double) * SRBM_PUSH_DOUBLES * B);
     }
+    if (ok && src->d_period) ok = hipMalloc(&h->d_period, sizeof(double) * B) == hipSuccess && cp(h->d_period, src->d_period, sizeof(double) * B);
     if (ok && src->d_wbc) ok = hipMalloc(&h->d_wbc, sizeof(SrbmWbcParams)) == hipSuccess && cp(h->d_wbc, src->d_wbc, sizeof(SrbmWbcParams));      // (a clone carries the complete state)
     // (the control tick's q_des_ goes along)
     if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
@@ -725,7 +730,7 @@ static int launch_fused(srbm_batch* h, const char* fn, int first_index, int step
 }
 int srbm_rti_advance(srbm_batch* h, int first_index, int steps) {
     if (!h || steps < 0) return fail("bad arguments");
-    return launch_fused(h, "srbm_rti_advance", first_index, steps, SrbmPlantArgs{nullptr, nullptr, nullptr, 1, 0, 0.0, 0.0});
+    return launch_fused(h, "srbm_rti_advance", first_index, steps, SrbmPlantArgs{nullptr, nullptr, h->d_dt, 1, 0, 0.0, 0.0});
 }
 
 // ---- closed-loop rollout harness (srbm_plant.hiph) ----
@@ -733,8 +738,8 @@ static int plant_alloc(srbm_batch* h) {
     if (h->d_plant) return 0;
     const size_t B = h->batch;
     HIPCHK(hipMalloc(&h->d_plant, sizeof(double) * 13 * B));
-    HIPCHK(hipMalloc(&h->d_push_time, sizeof(double) * B));
-    HIPCHK(hipMalloc(&h->d_push_impulse, sizeof(double) * 6 * B));
+    HIPCHK(hipMalloc(&h->d_push, sizeof(double) * SRBM_PUSH_DOUBLES * B));
+    HIPCHK(hipMemsetAsync(h->d_push, 0, sizeof(double) * SRBM_PUSH_DOUBLES * B, h->stream));          // (a clone copies it whether a push is set or not)
     return 0;
 }
 int srbm_plant_set_state(srbm_batch* h, const double* state) {
@@ -755,17 +760,47 @@ int srbm_plant_set_push(srbm_batch* h, const double* time, const double* impulse
     if (plant_alloc(h)) return -1;
     h->push_set = time != nullptr;
     if (time) {
-        HIPCHK(hipMemcpyAsync(h->d_push_time, time, sizeof(double) * h->batch, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_push_impulse, impulse, sizeof(double) * 6 * h->batch, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        std::vector<double> rec((size_t)SRBM_PUSH_DOUBLES * h->batch);          // one record {time, impulse[6]} per instance
+        for (int b = 0; b < h->batch; b++) {
+            rec[(size_t)b * SRBM_PUSH_DOUBLES] = time[b];
+            std::memcpy(&rec[(size_t)b * SRBM_PUSH_DOUBLES + 1], impulse + (size_t)b * 6, sizeof(double) * 6);
+        }
+        HIPCHK(hipMemcpyAsync(h->d_push, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));          // (rec leaves scope)
     }
     return 0;
+}
+// the MPC period of the closed-loop protocols, per instance; the open-loop entries never see it (their SrbmPlantArgs carry the array of dt)
+int srbm_plant_set_period(srbm_batch* h, const double* period) {
+    if (!h) return fail("srbm_plant_set_period: bad arguments (NULL handle)");
+    if (!period) { h->period.clear(); return 0; }          // (the device array stays allocated; the launches are handed the array of dt)
+    const double horizon = h->hp.N * h->hp.dt;
+    for (int b = 0; b < h->batch; b++)
+        if (!std::isfinite(period[b]) || period[b] <= 0.0 || period[b] >= horizon) {
+            char v[64]; std::snprintf(v, sizeof v, "%.17g", period[b]);
+            return fail("srbm_plant_set_period: the period of instance " + std::to_string(b) + " is " + v + ": a finite period in (0, num_nodes * dt = " +
+                        std::to_string(horizon) + ") is required (beyond it the plant would read past the trajectory)");
+        }
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->d_period) HIPCHK(hipMalloc(&h->d_period, sizeof(double) * h->batch));
+    HIPCHK(hipMemcpyAsync(h->d_period, period, sizeof(double) * h->batch, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->period.assign(period, period + h->batch);
+    return 0;
+}
+int srbm_plant_get_period(srbm_batch* h, double* period) {
+    if (!h || !period) return fail("srbm_plant_get_period: bad arguments");
+    for (int b = 0; b < h->batch; b++) period[b] = h->period.empty() ? h->hp.dt : h->period[b];
+    return 0;
+}
+// the plant arguments of a closed-loop launch
+static SrbmPlantArgs plant_args(const srbm_batch* h, int substeps, int advance_time) {
+    return SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push : nullptr, h->period.empty() ? h->d_dt : h->d_period, substeps, advance_time ? 1 : 0};
 }
 int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int substeps, int advance_time) {
     if (!h || steps < 0 || substeps < 1) return fail("bad arguments");
     if (!h->d_plant) return fail("the plant state has not been set (srbm_plant_set_state)");
-    return launch_fused(h, "srbm_closed_loop_advance", first_index, steps, SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push_time : nullptr, h->push_set ? h->d_push_impulse : nullptr,
-                                                              substeps, advance_time ? 1 : 0});
+    return launch_fused(h, "srbm_closed_loop_advance", first_index, steps, plant_args(h, substeps, advance_time));
 }
 // the same protocol, one kernel launch per phase and step (grid-wide synchronisation between the phases); kept for
 // A/B measurements against the fused kernel
@@ -1144,14 +1179,11 @@ int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_o
     return 0;
 }
 // ---- closed-loop rollout with the gait step (include/srbm_rti.h; srbm_gait_rollout.hiph) ----
-static SrbmPlantArgs plant_args(const srbm_batch* h, int substeps, int advance_time) {
-    return SrbmPlantArgs{h->d_plant, h->push_set ? h->d_push_time : nullptr, h->push_set ? h->d_push_impulse : nullptr, substeps, advance_time ? 1 : 0};
-}
 // the plant half of closed-loop iteration `index` on its own kernel: h->d_plant advanced, h->d_state / d_time / d_ee filled
 static int launch_plant(srbm_batch* h, int index, int substeps, int advance_time) {
     const SrbmPlantArgs pl = plant_args(h, substeps, advance_time);
-    hipLaunchKernelGGL(srbm_k_plant_inputs, dim3(h->batch), dim3(GR_PLANT_THREADS), 0, h->stream, h->dp, h->insts, index * h->hp.dt, pl.substeps, pl.advance_time,
-                       pl.plant, pl.push_time, pl.push_impulse, h->d_state, h->d_time, h->d_ee);
+    hipLaunchKernelGGL(srbm_k_plant_inputs, dim3(h->batch), dim3(GR_PLANT_THREADS), 0, h->stream, h->dp, h->insts, index, pl.period, pl.substeps, pl.advance_time,
+                       pl.plant, pl.push, h->d_state, h->d_time, h->d_ee);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1172,8 +1204,8 @@ static int log_gait_step(srbm_gait* g, int run) {
     h->log_used++;
     return 0;
 }
-// The controller loop of srbm_gait_rti_advance closed over the plant of srbm_closed_loop_advance: run r integrates the plant from (r - 1) dt to r dt
-// (iteration r - 1 of srbm_closed_loop_advance) and branches on r as srbm_gait_rti_advance does.  A maximal stretch of plain runs is ONE multi-step plant
+// The controller loop of srbm_gait_rti_advance closed over the plant of srbm_closed_loop_advance: run r integrates the plant from (r - 1) p to r p,
+// p the MPC period of the instance (iteration r - 1 of srbm_closed_loop_advance) and branches on r as srbm_gait_rti_advance does.  A maximal stretch of plain runs is ONE multi-step plant
 // launch (launch_fused: the step queues for a batch larger than the chip); gradient and line-search runs take the plant kernel, then the one-step kernels.
 int srbm_gait_closed_loop_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq, int substeps, int advance_time) {
     const char* fn = "srbm_gait_closed_loop_advance";

@@ -176,9 +176,14 @@ typedef struct SrbmWork {
 } SrbmWork;
 
 /* launch arguments of the fused RTI kernel (srbm_fused.hiph) besides the batch: the closed-loop mode (plant != nullptr, srbm_plant.hiph) and the two
-   settings of srbm_set_solver_step_rule */
+   settings of srbm_set_solver_step_rule.  push: one record {time, impulse[6]} per instance, push[batch][SRBM_PUSH_DOUBLES] (srbm_plant_set_push), nullptr:
+   no pushes -- one pointer, not one per array: every pointer of this list is live across the whole step loop of kernels that spill already.
+   period: the step of the time grid of every instance, period[batch], never nullptr: the MPC periods of srbm_plant_set_period in the closed-loop mode
+   where they are set, the batch's array of dt in every other launch (srbm_batch::d_dt) -- so the kernels read p = period[b] where they read Pp->dt
+   before, with no test of the pointer: whatever such a test needs would be formed before the step loop and stay live, and spilled, across the IPM */
+#define SRBM_PUSH_DOUBLES 7
 typedef struct SrbmPlantArgs {
-    double* plant; const double* push_time; const double* push_impulse;
+    double* plant; const double* push; const double* period;
     int substeps, advance_time;
     double tol_step, start_mu;
 } SrbmPlantArgs;

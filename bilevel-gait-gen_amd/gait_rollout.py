@@ -33,12 +33,14 @@ class GaitRollout:
         self.mpc, self.gait, self.L = mpc, gait, mpc.L
 
     def advance(self, first_run_num, steps, gait_opt_freq, substeps=1, advance_time=False):
-        """runs first_run_num .. first_run_num + steps - 1 (first_run_num >= 1: run r integrates the plant from (r - 1) dt to r dt); asynchronous"""
+        """runs first_run_num .. first_run_num + steps - 1 (first_run_num >= 1: run r of instance b integrates its plant from (r - 1) p over p and
+        solves at (r - 1) p + p, p its MPC period -- mpc_period.plant_set_period; the node step dt where none is set); gait_opt_freq counts runs; asynchronous"""
         self.mpc._chk(self.L.srbm_gait_closed_loop_advance(self.gait.g, int(first_run_num), int(steps), int(gait_opt_freq), int(substeps),
                                                            int(bool(advance_time))))
 
     def plant_advance(self, index, substeps=1, advance_time=False):
-        """the plant half of closed-loop iteration `index`, no solve: (state[batch][13], time[batch], ee[batch][4][3]) -- the inputs of the next solve"""
+        """the plant half of closed-loop iteration `index` (from index p over p, p the MPC period of the instance: dt unless set), no solve:
+        (state[batch][13], time[batch] = index p + p, ee[batch][4][3]) -- the inputs of the next solve"""
         m = self.mpc
         state, time, ee = np.zeros((m.batch, 13)), np.zeros(m.batch), np.zeros((m.batch, 4, 3))
         m._chk(self.L.srbm_plant_advance(m.h, int(index), int(substeps), int(bool(advance_time)), state.ctypes.data_as(_dp), time.ctypes.data_as(_dp),

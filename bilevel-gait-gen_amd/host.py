@@ -154,6 +154,8 @@ int srbm_rti_advance_unfused(srbm_batch*, int, int)
 int srbm_plant_set_state(srbm_batch*, double*)
 int srbm_plant_get_state(srbm_batch*, double*)
 int srbm_plant_set_push(srbm_batch*, double*, double*)
+int srbm_plant_set_period(srbm_batch*, double*)
+int srbm_plant_get_period(srbm_batch*, double*)
 int srbm_closed_loop_advance(srbm_batch*, int, int, int, int)
 int srbm_plant_advance(srbm_batch*, int, int, int, double*, double*, double*)
 int srbm_synchronize(srbm_batch*)
@@ -681,7 +683,7 @@ class BatchMPC:
     def rti_advance_unfused(self, first_index, steps):
         self._chk(self.L.srbm_rti_advance_unfused(self.h, int(first_index), int(steps)))
 
-    # ---- closed-loop rollout harness (include/srbm_rti.h: srbm_plant_*, srbm_closed_loop_advance) ----
+    # ---- closed-loop rollout harness (include/srbm_rti.h: srbm_plant_*, srbm_closed_loop_advance; the MPC period: mpc_period.py) ----
     def plant_set_state(self, state):
         self._chk(self.L.srbm_plant_set_state(self.h, _d(self._bcast(state, 13))))
 
@@ -696,6 +698,8 @@ class BatchMPC:
             self._chk(self.L.srbm_plant_set_push(self.h, _d(self._bcast(time, 1)), _d(self._bcast(impulse, 6))))
 
     def closed_loop_advance(self, first_index, steps, substeps=1, advance_time=False):
+        """iterations first_index .. first_index + steps - 1: iteration i of instance b integrates its plant from i p over p, p its MPC period
+        (mpc_period.plant_set_period; the node step dt where none is set), and solves at i p + p; asynchronous"""
         self._chk(self.L.srbm_closed_loop_advance(self.h, int(first_index), int(steps), int(substeps), int(bool(advance_time))))
 
     # ---- the step log: every step of a multi-step launch (include/srbm_rti.h: srbm_step_log_*) ----

@@ -115,6 +115,8 @@ int srbm_get_real_time_update_dev(srbm_batch* h, const double* state_dev, const 
 /* Device-resident open-loop protocol of test/gait_opt_playground.cpp:113-126: `steps` RTI iterations with
  * state := node 1 of the previous trajectory, foot locations := previous trajectory at t, t_i = (first_index+i)*dt.
  * No host round trip between iterations.  Asynchronous; srbm_synchronize() to wait.
+ * The open-loop entries (this one, srbm_rti_advance_unfused, srbm_gait_rti_advance) ignore srbm_plant_set_period: "state := node 1 of the previous
+ * trajectory" has no meaning at another period than the node step.
  * A batch of at most one instance per CU runs as one workgroup per instance for all steps; a LARGER batch with steps > 1 runs on a resident grid
  * that takes (instance, step) items from per-XCD queues (csrc/srbm_fused.hiph: the launch no longer ends with the instance whose `steps` solves
  * happen to be the longest) -- bitwise the same results (tests/test_gpu_queue.py), and bitwise those of the same steps launched one at a time
@@ -136,12 +138,29 @@ int srbm_rti_advance_unfused(srbm_batch* h, int first_index, int steps);
  *     if t < push_time <= t+dt:  lin-mom += impulse[0..2], ang-mom += impulse[3..5]
  *     MPC::GetRealTimeUpdate(x, t+dt, foot locations of the trajectory at t+dt)
  * srbm_plant_set_state: x[batch][13] (manifold state, as srbm_create_initial_run); srbm_plant_set_push: time[batch],
- * impulse[batch][6], both NULL to clear.  srbm_closed_loop_advance is asynchronous like srbm_rti_advance. */
+ * impulse[batch][6], both NULL to clear.  srbm_closed_loop_advance is asynchronous like srbm_rti_advance.
+ *
+ * The MPC period.  The reference's controller starts an update whenever the state sample is newer than the last one
+ * (MPCController::MPCUpdate, controllers/mpc_controller.cpp:299-346; the comparison against integrator_dt is commented out on line 308): the solve
+ * runs at the solve rate, the window shifts by a fraction of a node, the knots enter and leave it at arbitrary phases.  srbm_plant_set_period
+ * gives every instance its own period p = period[b]; srbm_closed_loop_advance, srbm_plant_advance and srbm_gait_closed_loop_advance then run
+ * iteration i (the gait entry: i = r - 1 of run r) of instance b as
+ *     time  = i * p
+ *     x    <- CalcIntegral(x, trajectory, time, substeps steps of p / substeps)
+ *     push if time < push_time <= time + p
+ *     solve at init_time = time + p, foot locations of the trajectory at time + p
+ * and gait_opt_freq keeps counting runs, as the reference's run_num does.  Without a call, after NULL, or with every entry equal to dt, all
+ * results are bitwise the same: the node step is the period where none is set.  Refused before anything is copied, the batch untouched and
+ * the message naming the instance: a period that is not finite, <= 0, or >= num_nodes * dt (the plant would read past the trajectory).
+ * srbm_batch_clone carries the setting.  The open-loop entries ignore it (see srbm_rti_advance). */
 int srbm_plant_set_state(srbm_batch* h, const double* state);
 int srbm_plant_get_state(srbm_batch* h, double* state);
 int srbm_plant_set_push(srbm_batch* h, const double* time, const double* impulse);
+/* MPC period of the closed-loop protocols, per instance: period[batch] seconds, NULL to clear (= the node step dt). */
+int srbm_plant_set_period(srbm_batch* h, const double* period);
+int srbm_plant_get_period(srbm_batch* h, double* period);   /* dt where none is set */
 int srbm_closed_loop_advance(srbm_batch* h, int first_index, int steps, int substeps, int advance_time);
-/* The plant half of iteration `index` on its own: integrate from index*dt to (index+1)*dt, apply the push, fill the device input buffers of the
+/* The plant half of iteration `index` on its own: integrate from index*p to index*p + p (p: the instance's MPC period, dt unless set), apply the push, fill the device input buffers of the
  * next solve -- and run NO solve.  Bitwise the inputs srbm_closed_loop_advance(h, index, 1, ..) hands to its solve, so a host may drive the loop
  * itself: srbm_plant_advance, then any entry that takes (state, init_time, ee).  Synchronous; outputs state[batch][13], time[batch] (= the
  * init_time of the next solve), ee[batch][4][3], any of them may be NULL.  Never logs. */
@@ -307,7 +326,7 @@ int srbm_gait_line_search(srbm_gait* g, const double* state, const double* init_
  * Asynchronous on the batch's stream; srbm_synchronize(h) to wait. */
 int srbm_gait_rti_advance(srbm_gait* g, int first_run_num, int steps, int gait_opt_freq);
 /* The same loop CLOSED over the plant of srbm_closed_loop_advance (controllers/mpc_controller.cpp:286-399: measured state in, one of the three
- * branches, out): for run r = first_run_num + i, r >= 1, t = r*dt
+ * branches, out): for run r = first_run_num + i, r >= 1, t = r*dt (with srbm_plant_set_period: t = (r - 1)*p + p and "dt" below is p, per instance)
  *   plant:      exactly iteration r - 1 of srbm_closed_loop_advance -- integrate from t - dt to t under the current trajectory (substeps,
  *               advance_time as there), the instance's push if t - dt < push_time <= t, then (plant state, t, foot locations of the current
  *               trajectory at t) to the solve;

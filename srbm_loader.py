@@ -1,5 +1,5 @@
 """Imports the modules of bilevel-gait-gen_amd/ (the directory name is not a Python identifier): `host` (ctypes binding of the C-ABI) and
-`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout` and `control_tick` (the entries beside host.py)."""
+`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick` and `mpc_period` (the entries beside host.py)."""
 import importlib.util
 import os
 import sys
@@ -23,3 +23,5 @@ gait_rollout = _load('srbm_gait_rollout', 'gait_rollout.py')
 sys.modules[__name__ + '.gait_rollout'] = gait_rollout
 control_tick = _load('srbm_control_tick', 'control_tick.py')
 sys.modules[__name__ + '.control_tick'] = control_tick
+mpc_period = _load('srbm_mpc_period', 'mpc_period.py')
+sys.modules[__name__ + '.mpc_period'] = mpc_period

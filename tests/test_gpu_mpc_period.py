@@ -1,0 +1,377 @@
+"""Closed-loop rollouts at an MPC period other than the node step (include/srbm_rti.h: srbm_plant_set_period, srbm_plant_get_period; through
+bilevel-gait-gen_amd/mpc_period.py).  All batches run in the mode (0, 0); the inputs are those tests/test_mpc_period_host.py holds to their conditions on
+the restatement alone (tests/mpc_period_kit.py).
+
+    1  no setting, NULL and an array of dt are one thing, bit for bit: multi-step launch with a log, and the gait loop;
+    2  one launch, single launches and the host-driven loop agree bitwise off the grid; field 1 of record i is i * p + p formed in numpy;
+    3  against the restatement, re-synchronised before every run (plant <= 1e-9, node states < REL_TOL, knot tables and (n, m) equal);
+    4  the gait loop at a period against PeriodLoop, re-synchronised; one call of 11 runs against 11 one-run calls at per-instance periods;
+    5  step queues: bitwise the results without them;
+    6  LARGE build: three steps in one launch against three launches;
+    7  refusals leave the batch untouched and name the instance; a clone carries the setting and continues bitwise."""
+import numpy as np
+import pytest
+
+from gait_rollout_kit import GRADIENT, LINE_SEARCH
+from gpu_kit import REL_TOL, relerr, same_bytes, status_ok_or_bad
+from mpc_period_kit import GAIT_CASES, GAIT_FREQ, GAIT_RUNS, NO_GAIT, PUSH, SUB, PeriodLoop, plain_case
+from oracle_py import load_config
+from srbm_loader import gait_rollout, host, mpc_period
+from srbm_loader.workloads import EE_NOMINAL, config_b_instance, instances
+
+pytestmark = pytest.mark.gpu
+MODE = (0.0, 0.0)
+F = host.STEP_LOG_FIELDS
+
+
+def rollout(g, log=0):
+    if log:
+        g.step_log_enable(log)
+    gait = host.BatchGaitOptimizer(g)
+    return gait, gait_rollout.GaitRollout(g, gait)
+
+
+def end_state(g, gait=None, records=False):
+    st, err = g.status()
+    out = dict(plant=g.plant_state(), states=g.trajectory_states(), x=g.qp_solution(), status=st, err=err, sizes=g.sizes(),
+               trajectory=np.frombuffer(bytes(g.get_trajectory()), np.uint8))           # (the knot tables among it)
+    if gait is not None:
+        out['contact_times'], out['counts'] = gait.contact_times()
+    if records:
+        out['records'] = g.step_log()
+    return out
+
+
+def assert_same(a, b, what, keys=None):
+    for k in keys or a:
+        same_bytes(a[k], b[k], '%s: %s' % (what, k))
+
+
+def config_b_batch():
+    """the four a1_configuration instances of the plain loop, cold-started, plant and pushes set; -> (cfg, base, periods)"""
+    cfg, states, ees, periods, push_times, impulses, _, _ = plain_case('config_b')
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    base.plant_set_state(states); base.plant_set_push(push_times, impulses)
+    return cfg, base, periods
+
+
+# ---- 1 ----
+def test_no_setting_null_and_an_array_of_dt_are_one_thing_multi_step_launch():
+    """8 instances with the pushes of test_closed_loop_fused_steps_equal_single_steps_and_push_distribution, 6 steps in one launch, with a log"""
+    cfg = load_config()
+    B, K = 8, 6
+    states, ees = instances(cfg, config_b_instance, B)
+    rng = np.random.default_rng(5)
+    pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    base.plant_set_state(states); base.plant_set_push(pt, imp)
+    res = {}
+    for how in ('none', 'null', 'dt'):
+        g = base.clone()
+        if how == 'null':
+            mpc_period.plant_set_period(g, 0.013); mpc_period.plant_set_period(g, None)
+        elif how == 'dt':
+            mpc_period.plant_set_period(g, np.full(B, cfg['integrator_dt']))
+        same_bytes(mpc_period.plant_period(g), np.full(B, cfg['integrator_dt']), how + ': the period read back')
+        g.step_log_enable(K)
+        g.closed_loop_advance(0, K, SUB, True); g.synchronize()
+        res[how] = end_state(g, records=True)
+        assert not res[how]['err'].any() and res[how]['records'].shape == (K, B, 64)
+        g.close()
+    assert_same(res['null'], res['none'], 'after NULL against no setting')
+    assert_same(res['dt'], res['none'], 'an array of dt against no setting')
+    assert np.abs(res['none']['plant'][:, 3:6] - states[:, 3:6]).max() > 0.5                      # (the pushes arrived)
+    base.close()
+
+
+def test_no_setting_null_and_an_array_of_dt_are_one_thing_gait_loop():
+    """the 3-instance inputs of test_gpu_gait_closed_loop.py through GaitRollout.advance(1, 11, 5, ..)"""
+    cfg, states, ees, _, push_times, impulses, _, _ = plain_case('config_b')
+    B = 3
+    base = host.BatchMPC.cold_start(cfg, states[:B], ees[:B], mode=MODE)
+    base.plant_set_state(states[:B]); base.plant_set_push(push_times[:B], impulses[:B])
+    res = {}
+    for how in ('none', 'null', 'dt'):
+        g = base.clone()
+        if how == 'null':
+            mpc_period.plant_set_period(g, [0.013, 0.02, 0.03]); mpc_period.plant_set_period(g)
+        elif how == 'dt':
+            mpc_period.plant_set_period(g, cfg['integrator_dt'])
+        gait, roll = rollout(g, log=GAIT_RUNS)
+        roll.advance(1, GAIT_RUNS, GAIT_FREQ, SUB, True); g.synchronize()
+        res[how] = end_state(g, gait, records=True)
+        res[how]['line_search'] = np.concatenate(roll.line_search_result(), axis=None)
+        assert not res[how]['err'].any()
+        gait.close(); g.close()
+    assert [int(k) for k in res['none']['records'][:, 0, 58]] == [0, 0, 0, 1, 2, 0, 0, 0, 1, 2, 0]
+    assert_same(res['null'], res['none'], 'after NULL against no setting')
+    assert_same(res['dt'], res['none'], 'dt for every instance against no setting')
+    base.close()
+
+
+# ---- 2 ----
+def test_one_launch_single_launches_and_the_host_driven_loop_agree_bitwise_off_the_grid():
+    cfg, base, periods = config_b_batch()
+    B, K = len(periods), 8
+    mpc_period.plant_set_period(base, periods)
+    same_bytes(mpc_period.plant_period(base), periods, 'the periods read back')
+    ga, gb, gc, gd = (base.clone() for _ in range(4))
+
+    ga.step_log_enable(K)
+    ga.closed_loop_advance(0, K, SUB, True); ga.synchronize()
+    rec = ga.step_log()
+    assert rec.shape == (K, B, 64) and not rec[:, :, 3].any()
+    for i in range(K):
+        same_bytes(rec[i, :, 1], i * periods + periods, 'step %d: init_time of the record against i * p + p' % i)
+    assert len({tuple(v) for v in rec[:, :, 5:7].reshape(-1, 2)}) > 1                             # (the window changed size on the way)
+
+    gb.step_log_enable(K)
+    for i in range(K):
+        gb.closed_loop_advance(i, 1, SUB, True)
+    gb.synchronize()
+    same_bytes(gb.step_log(), rec, 'records of eight one-step launches against one launch of eight')
+
+    gait_c, roll_c = rollout(gc)
+    for i in range(K):
+        state, time, ee = roll_c.plant_advance(i, SUB, True)
+        same_bytes(time, i * periods + periods, 'step %d: time of srbm_plant_advance against i * p + p' % i)
+        same_bytes(state, rec[i][:, F['state']], 'step %d: srbm_plant_advance state against the record' % i)
+        same_bytes(ee.reshape(B, 12), rec[i][:, F['ee']], 'step %d: srbm_plant_advance foot locations against the record' % i)
+        gc.get_real_time_update(state, time, ee)
+    gc.synchronize()
+
+    gd.closed_loop_advance(0, K, SUB, True); gd.synchronize()
+
+    ea = end_state(ga)
+    assert_same(end_state(gb), ea, 'eight one-step launches against one launch')
+    assert_same(end_state(gc), ea, 'the host-driven loop against one launch', keys=('plant', 'states', 'x', 'sizes', 'trajectory'))
+    assert_same(end_state(gd), ea, 'without a log against with one')
+    # the periods are in the result: instance 0 (p = dt) ran four times as long as instance 2
+    assert np.abs(ea['plant'][0, 3:6] - ea['plant'][2, 3:6]).max() > 0.5
+    gait_c.close()
+    for b in (ga, gb, gc, gd, base):
+        b.close()
+
+
+# ---- 3 ----
+@pytest.mark.parametrize('name,advance_time', [('config_b', 0), ('config_b', 1), ('config_d', 1)])
+def test_plain_loop_against_the_restatement_resynchronised(name, advance_time):
+    """Before every run the device is given the restatement's trajectories and plant states; after it: plant <= 1e-9 (identical records in: the
+    project's own figure for one plant step), node states < REL_TOL, knot tables and (n, m) equal, no error bits.  A second batch runs the same steps
+    free (one launch, never re-synchronised): its error at the end is printed, not asserted -- nobody has a figure for it off the grid."""
+    cfg, states, ees, periods, push_times, impulses, runs, adv = plain_case(name)
+    assert advance_time in adv
+    B = len(periods)
+    g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+    g.plant_set_state(states); g.plant_set_push(push_times, impulses)
+    mpc_period.plant_set_period(g, periods)
+    free = g.clone()
+    free.closed_loop_advance(0, runs, SUB, advance_time)
+    loops = [PeriodLoop(cfg, states[b], ees[b], NO_GAIT, SUB, advance_time, push_times[b], impulses[b], periods[b]) for b in range(B)]
+    seen = set()
+    for r in range(1, runs + 1):
+        g.set_warm_start_trajectory([l.o.trajectory_record(host) for l in loops])
+        g.plant_set_state(np.array([l.x for l in loops]))
+        outs = [l.run() for l in loops]
+        g.closed_loop_advance(r - 1, 1, SUB, advance_time); g.synchronize()
+        st, err = g.status()
+        assert not err.any(), (r, err)
+        plant, tr, sz = g.plant_state(), g.trajectory_states(), g.sizes()
+        for b, l in enumerate(loops):
+            e_plant, e_tr = relerr(plant[b], outs[b]['plant']), relerr(tr[b], l.o.states())
+            print('%s advance_time %d run %2d instance %d (p = %g): plant %.1e states %.1e' % (name, advance_time, r, b, periods[b], e_plant, e_tr))
+            assert e_plant <= 1e-9, (r, b, e_plant)
+            assert e_tr < REL_TOL, (r, b, e_tr)
+            osz = l.o.sizes()
+            assert (sz[b, 0], sz[b, 1]) == (osz['n'], osz['m']), (r, b, sz[b, :2], osz)
+            seen.add((osz['n'], osz['m']))
+            # (Solved / SolvedInacc / MaxIter steer the solve identically and which one an interior-point code reports is its own: gpu_kit.status_ok_or_bad)
+            assert l.o.stats()['status'] == 0 and status_ok_or_bad(st[b]) == 'ok', (r, b, st[b], l.o.stats()['status'])
+            kg = g.knots(b)
+            for e in range(4):
+                ko = l.o.knots(e)
+                assert kg['nk'][e] == ko['K'] and np.array_equal(kg['times'][e, :ko['K']], ko['times']), (r, b, e)
+    assert len(seen) > 1, seen
+    free.synchronize()
+    fp, ft = free.plant_state(), free.trajectory_states()
+    for b, l in enumerate(loops):
+        print('%s advance_time %d free-running after %d runs, instance %d (p = %g): plant %.1e states %.1e (not asserted)' %
+              (name, advance_time, runs, b, periods[b], relerr(fp[b], l.x), relerr(ft[b], l.o.states())))
+    free.close(); g.close()
+
+
+# ---- 4 ----
+@pytest.mark.parametrize('cfgname,push_time,period', GAIT_CASES)
+def test_gait_loop_at_a_period_against_the_restatement_resynchronised(cfgname, push_time, period):
+    """test_closed_loop_with_gait_step_against_the_restatement_resynchronised at an MPC period: two identical instances, 11 runs, a push; kinds, ready
+    flag, LP status and argmin compared at both line searches (checked on the CPU for exactly these inputs, tests/test_mpc_period_host.py: a ready
+    gradient and a solved LP at runs 4 and 9, the two cheapest candidates more than 1e-4 apart at both line searches)"""
+    FREQ, RUNS = GAIT_FREQ, GAIT_RUNS
+    cfg = load_config(cfgname)
+    s0 = np.array(cfg['srb_init'], float)
+    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=MODE)
+    g.plant_set_state(s0); g.plant_set_push(push_time, PUSH)
+    mpc_period.plant_set_period(g, period)
+    gait, roll = rollout(g, log=RUNS)
+    loop = PeriodLoop(cfg, s0, EE_NOMINAL, FREQ, SUB, 1, push_time, PUSH, period)
+    n_ls = n_argmin = 0
+    for r in range(1, RUNS + 1):
+        g.set_warm_start_trajectory([loop.o.trajectory_record(host)] * 2)
+        g.plant_set_state(loop.x)
+        out = loop.run()
+        roll.advance(r, 1, FREQ, SUB, True); g.synchronize()
+        if out['step'] is not None:
+            nv = int(gait.contact_times()[1][0].sum())
+            gait.set_step(out['step'][:nv])
+        st, err = g.status()
+        assert not err.any(), (r, err)
+        plant, tr = g.plant_state(), g.trajectory_states()
+        e_plant, e_tr = relerr(plant[0], out['plant']), relerr(tr[0], loop.o.states())
+        print('%s p = %g run %2d kind %d: plant %.1e states %.1e' % (cfgname, period, r, out['kind'], e_plant, e_tr))
+        assert np.array_equal(plant[0], plant[1]) and np.array_equal(tr[0], tr[1]), r
+        assert e_plant <= 1e-9, (r, e_plant)
+        assert e_tr < REL_TOL, (r, e_tr)
+        kg = g.knots(0)
+        same_bytes(np.frombuffer(bytes(g.get_trajectory(0, 1)), np.uint8), np.frombuffer(bytes(g.get_trajectory(1, 1)), np.uint8), 'run %d: the two instances' % r)
+        for e in range(4):
+            ko = loop.o.knots(e)
+            assert kg['nk'][e] == ko['K'] and np.array_equal(kg['times'][e, :ko['K']], ko['times']), (r, e)
+        rec = g.step_log(r - 1, 1)[0]
+        same_bytes(rec[0], rec[1], 'run %d: the records of the two instances' % r)
+        same_bytes(rec[:, 1], np.full(2, (r - 1) * period + period), 'run %d: init_time of the record' % r)
+        fields = gait_rollout.gait_fields_from_log(rec[0])
+        assert fields['kind'] == out['kind'], (r, fields, out['kind'])
+        if out['kind'] == GRADIENT:
+            assert fields['ready'] == int(out['ready']) == 1 and fields['lp_status'] == 0, (r, fields)
+        if out['kind'] == LINE_SEARCH:
+            n_ls += 1
+            imin, costs = roll.line_search_result()
+            assert imin[0] == imin[1] == fields['imin']
+            srt = np.sort(out['costs'])
+            print('   line search: device imin %d, restatement %d; its two cheapest candidates %.3e apart (relative)' %
+                  (imin[0], out['imin'], (srt[1] - srt[0]) / max(1.0, abs(srt[0]))))
+            if srt[1] - srt[0] > 1e-4 * max(1.0, abs(srt[0])):
+                n_argmin += 1
+                assert imin[0] == out['imin'], (r, imin[0], out['imin'], costs[0], out['costs'])
+    assert n_ls == 2 and n_argmin == 2, (n_ls, n_argmin)
+    gait.close(); g.close()
+
+
+def test_gait_loop_one_call_against_single_calls_at_per_instance_periods():
+    cfg = load_config('a1_configuration')
+    s0 = np.array(cfg['srb_init'], float)
+    periods = np.array([0.013, 0.03])
+    base = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=MODE)
+    base.plant_set_state(s0); base.plant_set_push(0.03, PUSH)
+    mpc_period.plant_set_period(base, periods)
+    ga, gb = base.clone(), base.clone()
+    gait_a, roll_a = rollout(ga, log=GAIT_RUNS)
+    roll_a.advance(1, GAIT_RUNS, GAIT_FREQ, SUB, True); ga.synchronize()
+    gait_b, roll_b = rollout(gb, log=GAIT_RUNS)
+    for r in range(1, GAIT_RUNS + 1):
+        roll_b.advance(r, 1, GAIT_FREQ, SUB, True)
+    gb.synchronize()
+    ea, eb = end_state(ga, gait_a, records=True), end_state(gb, gait_b, records=True)
+    assert_same(eb, ea, '11 one-run calls against one call of 11 runs')
+    assert not ea['err'].any()
+    for r in range(1, GAIT_RUNS + 1):
+        same_bytes(ea['records'][r - 1, :, 1], (r - 1) * periods + periods, 'run %d: init_time of the record' % r)
+    assert not np.array_equal(ea['plant'][0], ea['plant'][1])
+    gait_a.close(); gait_b.close()
+    for b in (ga, gb, base):
+        b.close()
+
+
+# ---- 5 ----
+def test_step_queues_at_mixed_periods_are_bitwise_the_per_instance_launch(monkeypatch):
+    """CU count + 4 instances, periods cycling through [0.05, 0.025, 0.013], 6 steps: the time of an item is that of its instance"""
+    cfg = load_config()
+    probe = host.BatchMPC(cfg, 1)
+    n_cu = probe.debug_launch_info()['n_cu']
+    probe.close()
+    B, K = n_cu + 4, 6
+    states, ees = instances(cfg, config_b_instance, B)
+    periods = np.array([0.05, 0.025, 0.013])[np.arange(B) % 3]
+    pt = np.full(B, 1e9); pt[::7] = 0.07
+    imp = np.zeros((B, 6)); imp[::7, 0] = 1.5; imp[::7, 1] = -1.0
+    res = {}
+    for no_queue in (False, True):
+        if no_queue:
+            monkeypatch.setenv('SRBM_NO_STEP_QUEUE', '1')
+        else:
+            monkeypatch.delenv('SRBM_NO_STEP_QUEUE', raising=False)
+        g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
+        g.plant_set_state(states); g.plant_set_push(pt, imp)
+        mpc_period.plant_set_period(g, periods)
+        g.step_log_enable(K)
+        g.closed_loop_advance(0, K, SUB, True); g.synchronize()
+        info = g.debug_launch_info()
+        assert info == dict(n_cu=n_cu, kernel='srbm_rti_fused' if no_queue else 'srbm_rti_queued', steps=K, queued=not no_queue), info
+        res[no_queue] = end_state(g, records=True)
+        assert not res[no_queue]['err'].any()
+        g.close()
+    assert_same(res[False], res[True], 'step queues against one workgroup per instance')
+    for i in range(K):
+        same_bytes(res[False]['records'][i, :, 1], i * periods + periods, 'step %d: init_time per item' % i)
+
+
+# ---- 6 ----
+def test_large_build_one_launch_against_three_launches():
+    cfg = load_config()
+    states, ees = instances(cfg, config_b_instance, 2)
+    periods = np.array([0.013, 0.05])
+    base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE, large=True)
+    assert base.large
+    base.plant_set_state(states); base.plant_set_push([0.03, 0.07], [PUSH, -PUSH])
+    mpc_period.plant_set_period(base, periods)
+    ga, gb = base.clone(), base.clone()
+    ga.step_log_enable(3); gb.step_log_enable(3)
+    ga.closed_loop_advance(0, 3, SUB, True); ga.synchronize()
+    for i in range(3):
+        gb.closed_loop_advance(i, 1, SUB, True)
+    gb.synchronize()
+    ea = end_state(ga, records=True)
+    assert_same(end_state(gb, records=True), ea, 'LARGE build: three launches against one')
+    assert not ea['err'].any()
+    for i in range(3):
+        same_bytes(ea['records'][i, :, 1], i * periods + periods, 'step %d: init_time of the record' % i)
+    for b in (ga, gb, base):
+        b.close()
+
+
+# ---- 7 ----
+def test_refusals_leave_the_batch_untouched_and_a_clone_carries_the_setting():
+    cfg, g, periods = config_b_batch()
+    B = len(periods)
+    dt, N = cfg['integrator_dt'], cfg['num_nodes']
+    g.step_log_enable(4)
+    mpc_period.plant_set_period(g, periods)
+    g.closed_loop_advance(0, 1, SUB, True); g.synchronize()
+    plant, traj, before = g.plant_state(), bytes(g.get_trajectory()), end_state(g)
+    for b, bad in enumerate((0.0, -0.013, float('nan'), N * dt)):
+        per = periods.copy(); per[b] = bad
+        with pytest.raises(RuntimeError, match=r'srbm_plant_set_period: the period of instance %d\b' % b):
+            mpc_period.plant_set_period(g, per)
+        g.synchronize()
+        same_bytes(mpc_period.plant_period(g), periods, 'the periods after the refusal of %r' % bad)
+        same_bytes(g.plant_state(), plant, 'plant state after the refusal of %r' % bad)
+        assert bytes(g.get_trajectory()) == traj and g.step_log_count() == 1, bad
+    with pytest.raises(RuntimeError, match='instance 0'):
+        mpc_period.plant_set_period(g, float('inf'))
+    assert_same(end_state(g), before, 'the batch after the refusals')
+    # the largest period below the horizon is accepted by the entry (and the setting replaced)
+    mpc_period.plant_set_period(g, np.nextafter(N * dt, 0.0)); mpc_period.plant_set_period(g, periods)
+    # a clone returns the same periods and continues bitwise like its source; the open-loop entry ignores the setting
+    c = g.clone()
+    same_bytes(mpc_period.plant_period(c), periods, 'the periods of the clone')
+    c.step_log_enable(4)
+    g.closed_loop_advance(1, 3, SUB, True); c.closed_loop_advance(1, 3, SUB, True)
+    g.synchronize(); c.synchronize()
+    assert_same(end_state(c), end_state(g), 'the clone against its source after three more steps')
+    same_bytes(c.step_log(), g.step_log(1, 3), 'the records of the clone against its source')
+    o1, o2 = g.clone(), g.clone()
+    mpc_period.plant_set_period(o2, None)
+    o1.rti_advance(4, 2); o2.rti_advance(4, 2); o1.synchronize(); o2.synchronize()
+    assert_same(end_state(o1), end_state(o2), 'srbm_rti_advance with a period set against none')
+    for b in (o1, o2, c, g):
+        b.close()
