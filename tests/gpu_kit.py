@@ -1,16 +1,19 @@
 """What the GPU tests and the developer scripts share beyond the package's own helpers (workloads.instances, workloads.EE_NOMINAL,
 BatchMPC.cold_start): tolerances, comparisons and small drivers.  A plain module: no fixtures, nothing pytest collects.
 
-    REL_TOL, relerr             every parity module (parity, resync, gait, large, ownpath, closed_loop, instance_params, dense_rows; gpu_protocols)
+    REL_TOL, relerr             every parity module (parity, resync, gait, large, ownpath, closed_loop, mpc_period, instance_params, dense_rows;
+                                gpu_protocols, closed_loop_kit), test_lp_reference_host
     EE_TEST                     test_gpu_parity, test_oracle_mpc
-    status_ok_or_bad            test_gpu_parity (there as status_class)
+    status_ok_or_bad            test_gpu_parity (there as status_class), test_gpu_mpc_period
     status_four_classes         gpu_protocols.resync_protocol (there as cls)
     advance, snapshot,
     assert_bitwise              gpu_protocols.run_case, test_gpu_step_log
-    same_bytes                  test_gpu_step_log; through assert_rows_bitwise: test_gpu_instance_params
+    same_bytes                  test_gpu_step_log, test_gpu_gait_lp, test_gpu_gait_closed_loop, test_gpu_mpc_period, closed_loop_kit (assert_same);
+                                through assert_rows_bitwise: test_gpu_instance_params
     wbc_inputs                  test_gpu_wbc, scripts/dev_prof_wbc.py
 
-The two long drivers (run_case, make_batch / resync_protocol) are in tests/gpu_protocols.py."""
+The two long drivers (run_case, make_batch / resync_protocol) are in tests/gpu_protocols.py; what the closed-loop tests share (the CPU restatement
+of the loop, its inputs, the comparisons of two batches) is in tests/closed_loop_kit.py."""
 import ctypes as C
 
 import numpy as np

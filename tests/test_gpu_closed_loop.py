@@ -2,33 +2,18 @@
 
 The plant is RKIntegrator::CalcIntegral (/root/reference/mpc/rk_integrator.cpp:14-30) over SingleRigidBodyModel::CalcDynamics
 (/root/reference/mpc/models/single_rigid_body_model.cpp:222-256) under the forces / foot locations of the current
-trajectory; the oracle restates both (oracle/srbm_traj_model.hpp: CalcDynamics, CalcIntegral).  Tolerances: plant states and
-trajectories <= 1e-4 relative (the north-star tolerance; a plant step alone agrees to 1e-12)."""
+trajectory; the oracle restates both (oracle/srbm_traj_model.hpp: CalcDynamics, CalcIntegral), tests/closed_loop_kit.py the loop around them
+(RestatementLoop).  Tolerances: plant states and trajectories <= 1e-4 relative (the north-star tolerance; a plant step alone agrees to 1e-12)."""
 import numpy as np
 import pytest
 
+from closed_loop_kit import IMPULSES, NO_GAIT, PUSH_TIMES, RestatementLoop, push_draw
 from gpu_kit import REL_TOL, relerr
-from oracle_py import OracleMPC, load_config
+from oracle_py import load_config
 from srbm_loader import host
 from srbm_loader.workloads import config_b_instance, config_d_instance, instances
 
 pytestmark = pytest.mark.gpu
-
-
-def oracle_closed_loop(cfg, state, ee, steps, substeps, advance_time, push_time, impulse):
-    o = OracleMPC(cfg); o.set_warmstart(state); o.initial_run(state, ee)
-    dt = cfg['integrator_dt']
-    x = np.array(state, float)
-    plant = []
-    for i in range(steps):
-        t = i * dt
-        x = o.plant_integrate(x, t, dt / substeps, substeps, advance_time)
-        if t < push_time <= t + dt:
-            x[3:6] += impulse[:3]; x[10:13] += impulse[3:]
-        plant.append(x.copy())
-        eev = np.array([[o.ee_value(e, 1, c, t + dt) for c in range(3)] for e in range(4)])
-        o.rti(x, t + dt, eev)
-    return o, np.array(plant)
 
 
 @pytest.mark.parametrize('advance_time', [0, 1])
@@ -36,8 +21,7 @@ def test_closed_loop_rollout_matches_oracle(advance_time):
     cfg = load_config()
     B, K, SUB = 3, 6, 5
     states, ees = instances(cfg, config_b_instance, B)
-    push_time = np.array([0.12, 0.07, 1e9])                      # instance 2 is never pushed
-    impulse = np.array([[2.5, -1.0, 0.3, 0.05, -0.1, 0.2], [-1.5, 2.0, 0.0, 0.0, 0.1, -0.1], [9, 9, 9, 9, 9, 9]], float)
+    push_time, impulse = PUSH_TIMES[:B], IMPULSES[:B]             # instance 2 is never pushed
     g = host.BatchMPC.cold_start(cfg, states, ees)
     g.plant_set_state(states); g.plant_set_push(push_time, impulse)
     for i in range(K):                                           # one step per call: the plant state after every step is compared
@@ -47,7 +31,9 @@ def test_closed_loop_rollout_matches_oracle(advance_time):
     assert np.all(err == 0)
     xs, tr = g.plant_state(), g.trajectory_states()
     for b in range(B):
-        o, plant = oracle_closed_loop(cfg, states[b], ees[b].reshape(4, 3), K, SUB, advance_time, push_time[b], impulse[b])
+        loop = RestatementLoop(cfg, states[b], ees[b].reshape(4, 3), NO_GAIT, SUB, advance_time, push_time[b], impulse[b])
+        plant = [loop.run()['plant'] for _ in range(K)]
+        o = loop.o
         assert relerr(first[b], plant[0]) < 1e-6                 # first plant step: the trajectories of the two cold starts agree to ~1e-6 (observed 8e-8)
         assert relerr(xs[b], plant[-1]) < REL_TOL
         assert relerr(tr[b], o.states()) < REL_TOL
@@ -62,8 +48,7 @@ def test_closed_loop_fused_steps_equal_single_steps_and_push_distribution():
     cfg = load_config()
     B, K = 8, 6
     states, ees = instances(cfg, config_b_instance, B)
-    rng = np.random.default_rng(5)
-    pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
+    pt, imp, rng = push_draw()
     res = []
     for one_launch in (True, False):
         g = host.BatchMPC.cold_start(cfg, states, ees)
@@ -80,7 +65,7 @@ def test_closed_loop_fused_steps_equal_single_steps_and_push_distribution():
     g = host.BatchMPC(cfg, 2)
     with pytest.raises(RuntimeError):
         g.closed_loop_advance(0, 1, 1, False)
-    # Config D sizes
+    # Config D sizes (its pushes drawn from the same generator, after the eight)
     cfgd = load_config('a1_config_distr_rejection')
     B = 16
     states, ees = instances(cfgd, config_d_instance, B)

@@ -10,39 +10,16 @@ srbm_gait_get_line_search_result; csrc/srbm_gait_rollout.hiph), through bilevel-
 import numpy as np
 import pytest
 
-from gait_rollout_kit import GRADIENT, LINE_SEARCH, PLAIN, RestatementLoop
-from gpu_kit import REL_TOL, relerr, same_bytes
+from closed_loop_kit import (GRADIENT, IMPULSES, LINE_SEARCH, MODE, PLAIN, PUSH, PUSH_TIMES, SUB, assert_same, chip_cu_count, end_state, push_draw,
+                             resync_gait_loop, rollout, step_queues_on_and_off)
+from gpu_kit import same_bytes
 from oracle_py import load_config
 from srbm_loader import gait_rollout, host
-from srbm_loader.workloads import EE_NOMINAL, config_b_instance, instances
+from srbm_loader.workloads import config_b_instance, instances
 
 pytestmark = pytest.mark.gpu
-MODE = (0.0, 0.0)
-SUB = 4
 F = host.STEP_LOG_FIELDS
 GF = gait_rollout.GAIT_LOG_FIELDS
-
-
-def rollout(g, log=0):
-    """the gait optimiser and the rollout of a batch whose plant is set; log: room for that many runs"""
-    if log:
-        g.step_log_enable(log)
-    gait = host.BatchGaitOptimizer(g)
-    return gait, gait_rollout.GaitRollout(g, gait)
-
-
-def end_state(g, gait=None):
-    st, err = g.status()
-    out = dict(plant=g.plant_state(), states=g.trajectory_states(), x=g.qp_solution(), status=st, err=err,
-               trajectory=np.frombuffer(bytes(g.get_trajectory()), np.uint8))           # (the knot tables among it)
-    if gait is not None:
-        out['contact_times'], out['counts'] = gait.contact_times()
-    return out
-
-
-def assert_same(a, b, what, keys=None):
-    for k in keys or a:
-        same_bytes(a[k], b[k], '%s: %s' % (what, k))
 
 
 @pytest.mark.parametrize('advance_time', [False, True], ids=['time_held', 'time_advanced'])
@@ -52,8 +29,7 @@ def test_plain_runs_are_bitwise_the_closed_loop_advance(advance_time):
     cfg = load_config()
     B, K = 8, 6
     states, ees = instances(cfg, config_b_instance, B)
-    rng = np.random.default_rng(5)
-    pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
+    pt, imp, _ = push_draw()
     base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
     base.plant_set_state(states); base.plant_set_push(pt, imp)
     twin, g = base.clone(), base.clone()
@@ -72,9 +48,9 @@ def test_plain_runs_are_bitwise_the_closed_loop_advance(advance_time):
 
 
 # config_b instances 0..2 under these pushes: the CPU restatement's own closed loop has a valid gradient and a solved LP at runs 4 and 9 for each of
-# them (checked with tests/gait_rollout_kit.py before they were chosen; instance 2 is never pushed)
-PUSH_TIME_3 = np.array([0.12, 0.07, 1e9])
-IMPULSE_3 = np.array([[2.5, -1.0, 0.3, 0.05, -0.1, 0.2], [-1.5, 2.0, 0.0, 0.0, 0.1, -0.1], [9, 9, 9, 9, 9, 9]], float)
+# them (checked with RestatementLoop before they were chosen; instance 2 is never pushed)
+PUSH_TIME_3 = PUSH_TIMES[:3]
+IMPULSE_3 = IMPULSES[:3]
 
 
 def test_one_call_single_calls_and_the_host_driven_loop_agree_bitwise():
@@ -161,9 +137,6 @@ def test_one_call_single_calls_and_the_host_driven_loop_agree_bitwise():
         b.close()
 
 
-PUSH = np.array([1.5, -1.0, 0.2, 0.03, -0.05, 0.1])
-
-
 @pytest.mark.parametrize('cfgname,push_time', [('a1_gait_opt_config', 0.05), ('a1_configuration', 0.12)])
 def test_closed_loop_with_gait_step_against_the_restatement_resynchronised(cfgname, push_time):
     """The closed-loop twin of test_controller_loop_with_gait_step with resync=True: two identical instances, 11 runs, a push.  Before every run the
@@ -171,79 +144,27 @@ def test_closed_loop_with_gait_step_against_the_restatement_resynchronised(cfgna
     test_contact_time_lp_matches_oracle).  Checked on the CPU for exactly these inputs: the restatement has a valid gradient and a solved LP at runs
     4 and 9 in both configurations, and at all four line searches its two cheapest candidates are more than 1e-4 apart (the closest: 1.1e-3), so
     the argmin is compared every time."""
-    FREQ, RUNS = 5, 11
-    cfg = load_config(cfgname)
-    s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=MODE)
-    g.plant_set_state(s0); g.plant_set_push(push_time, PUSH)
-    gait, roll = rollout(g, log=RUNS)
-    loop = RestatementLoop(cfg, s0, EE_NOMINAL, FREQ, SUB, 1, push_time, PUSH)
-    n_ls = n_argmin = 0
-    for r in range(1, RUNS + 1):
-        g.set_warm_start_trajectory([loop.o.trajectory_record(host)] * 2)
-        g.plant_set_state(loop.x)
-        out = loop.run()
-        roll.advance(r, 1, FREQ, SUB, True); g.synchronize()
-        if out['step'] is not None:
-            nv = int(gait.contact_times()[1][0].sum())
-            gait.set_step(out['step'][:nv])
-        st, err = g.status()
-        assert not err.any(), (r, err)
-        plant, tr = g.plant_state(), g.trajectory_states()
-        e_plant, e_tr = relerr(plant[0], out['plant']), relerr(tr[0], loop.o.states())
-        print('%s run %2d kind %d: plant %.1e states %.1e' % (cfgname, r, out['kind'], e_plant, e_tr))
-        assert np.array_equal(plant[0], plant[1]) and np.array_equal(tr[0], tr[1]), r
-        assert e_plant <= 1e-9, (r, e_plant)             # identical records in: the project's own figure for one plant step is 1e-12
-        assert e_tr < REL_TOL, (r, e_tr)
-        kg = g.knots(0)
-        same_bytes(np.frombuffer(bytes(g.get_trajectory(0, 1)), np.uint8), np.frombuffer(bytes(g.get_trajectory(1, 1)), np.uint8), 'run %d: the two instances' % r)
-        for e in range(4):
-            ko = loop.o.knots(e)
-            assert kg['nk'][e] == ko['K'] and np.array_equal(kg['times'][e, :ko['K']], ko['times']), (r, e)
-        rec = g.step_log(r - 1, 1)[0]
-        same_bytes(rec[0], rec[1], 'run %d: the records of the two instances' % r)
-        fields = gait_rollout.gait_fields_from_log(rec[0])
-        assert fields['kind'] == out['kind'], (r, fields, out['kind'])
-        if out['kind'] == GRADIENT:
-            assert fields['ready'] == int(out['ready']) == 1 and fields['lp_status'] == 0, (r, fields)
-        if out['kind'] == LINE_SEARCH:
-            n_ls += 1
-            imin, costs = roll.line_search_result()
-            assert imin[0] == imin[1] == fields['imin']
-            srt = np.sort(out['costs'])
-            print('   line search: device imin %d, restatement %d; its two cheapest candidates %.3e apart (relative)' %
-                  (imin[0], out['imin'], (srt[1] - srt[0]) / max(1.0, abs(srt[0]))))
-            if srt[1] - srt[0] > 1e-4 * max(1.0, abs(srt[0])):
-                n_argmin += 1
-                assert imin[0] == out['imin'], (r, imin[0], out['imin'], costs[0], out['costs'])
-    assert n_ls == 2 and n_argmin == 2, (n_ls, n_argmin)
-    g.close()
+    resync_gait_loop(cfgname, push_time)
 
 
 def test_a_batch_larger_than_the_chip_takes_the_step_queues_in_its_plain_stretch(monkeypatch):
     """CU count + 4 instances, N = 20, runs 1..5 with gait_opt_freq 5: the three plain runs are one queued launch; against a batch created with the
     step queues switched off (the switch is read when a batch is created)"""
     cfg = load_config()
-    probe = host.BatchMPC(cfg, 1)
-    n_cu = probe.debug_launch_info()['n_cu']
-    probe.close()
+    n_cu = chip_cu_count()
     B = n_cu + 4
     states, ees = instances(cfg, config_b_instance, B)
     pt = np.full(B, 1e9); pt[::7] = 0.07
     imp = np.zeros((B, 6)); imp[::7, 0] = 1.5; imp[::7, 1] = -1.0
     res = {}
-    for no_queue in (False, True):
-        if no_queue:
-            monkeypatch.setenv('SRBM_NO_STEP_QUEUE', '1')
-        else:
-            monkeypatch.delenv('SRBM_NO_STEP_QUEUE', raising=False)
+    for no_queue in step_queues_on_and_off(monkeypatch):
         g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
         g.plant_set_state(states); g.plant_set_push(pt, imp)
         gait, roll = rollout(g, log=5)
         roll.advance(1, 5, 5, SUB, True); g.synchronize()
         info = g.debug_launch_info()
         assert info == dict(n_cu=n_cu, kernel='srbm_rti_fused' if no_queue else 'srbm_rti_queued', steps=3, queued=not no_queue), info
-        res[no_queue] = dict(end_state(g, gait), records=g.step_log())
+        res[no_queue] = end_state(g, gait, records=True)
         assert not res[no_queue]['err'].any()
         g.close()
     assert_same(res[False], res[True], 'step queues against one workgroup per instance')

@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from closed_loop_kit import chip_cu_count
 from gpu_kit import REL_TOL, assert_rows_bitwise, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
@@ -129,9 +130,7 @@ def run_child(B, steps, no_queue, path):
 
 
 def test_queued_heterogeneous_batch_is_bitwise_the_per_instance_launch():
-    probe = host.BatchMPC(load_config('a1_configuration'), 1)
-    n_cu = probe.debug_launch_info()['n_cu']
-    probe.close()
+    n_cu = chip_cu_count()
     B, steps = n_cu + 8, 3
     with tempfile.TemporaryDirectory() as tmp:
         queued, a = run_child(B, steps, False, os.path.join(tmp, 'q.npz'))

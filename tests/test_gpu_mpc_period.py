@@ -1,50 +1,26 @@
 """Closed-loop rollouts at an MPC period other than the node step (include/srbm_rti.h: srbm_plant_set_period, srbm_plant_get_period; through
 bilevel-gait-gen_amd/mpc_period.py).  All batches run in the mode (0, 0); the inputs are those tests/test_mpc_period_host.py holds to their conditions on
-the restatement alone (tests/mpc_period_kit.py).
+the restatement alone (tests/closed_loop_kit.py).
 
     1  no setting, NULL and an array of dt are one thing, bit for bit: multi-step launch with a log, and the gait loop;
     2  one launch, single launches and the host-driven loop agree bitwise off the grid; field 1 of record i is i * p + p formed in numpy;
     3  against the restatement, re-synchronised before every run (plant <= 1e-9, node states < REL_TOL, knot tables and (n, m) equal);
-    4  the gait loop at a period against PeriodLoop, re-synchronised; one call of 11 runs against 11 one-run calls at per-instance periods;
+    4  the gait loop at a period against RestatementLoop, re-synchronised; one call of 11 runs against 11 one-run calls at per-instance periods;
     5  step queues: bitwise the results without them;
     6  LARGE build: three steps in one launch against three launches;
     7  refusals leave the batch untouched and name the instance; a clone carries the setting and continues bitwise."""
 import numpy as np
 import pytest
 
-from gait_rollout_kit import GRADIENT, LINE_SEARCH
+from closed_loop_kit import (GAIT_CASES, GAIT_FREQ, GAIT_RUNS, MODE, NO_GAIT, PUSH, SUB, RestatementLoop, assert_same, chip_cu_count, end_state,
+                             plain_case, push_draw, resync_gait_loop, rollout, step_queues_on_and_off)
 from gpu_kit import REL_TOL, relerr, same_bytes, status_ok_or_bad
-from mpc_period_kit import GAIT_CASES, GAIT_FREQ, GAIT_RUNS, NO_GAIT, PUSH, SUB, PeriodLoop, plain_case
 from oracle_py import load_config
-from srbm_loader import gait_rollout, host, mpc_period
+from srbm_loader import host, mpc_period
 from srbm_loader.workloads import EE_NOMINAL, config_b_instance, instances
 
 pytestmark = pytest.mark.gpu
-MODE = (0.0, 0.0)
 F = host.STEP_LOG_FIELDS
-
-
-def rollout(g, log=0):
-    if log:
-        g.step_log_enable(log)
-    gait = host.BatchGaitOptimizer(g)
-    return gait, gait_rollout.GaitRollout(g, gait)
-
-
-def end_state(g, gait=None, records=False):
-    st, err = g.status()
-    out = dict(plant=g.plant_state(), states=g.trajectory_states(), x=g.qp_solution(), status=st, err=err, sizes=g.sizes(),
-               trajectory=np.frombuffer(bytes(g.get_trajectory()), np.uint8))           # (the knot tables among it)
-    if gait is not None:
-        out['contact_times'], out['counts'] = gait.contact_times()
-    if records:
-        out['records'] = g.step_log()
-    return out
-
-
-def assert_same(a, b, what, keys=None):
-    for k in keys or a:
-        same_bytes(a[k], b[k], '%s: %s' % (what, k))
 
 
 def config_b_batch():
@@ -61,8 +37,7 @@ def test_no_setting_null_and_an_array_of_dt_are_one_thing_multi_step_launch():
     cfg = load_config()
     B, K = 8, 6
     states, ees = instances(cfg, config_b_instance, B)
-    rng = np.random.default_rng(5)
-    pt = rng.uniform(0.0, 0.3, B); imp = rng.normal(0, 1.0, (B, 6)) * np.array([2.5, 2.5, 0.5, 0.2, 0.2, 0.2])
+    pt, imp, _ = push_draw()
     base = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
     base.plant_set_state(states); base.plant_set_push(pt, imp)
     res = {}
@@ -167,7 +142,7 @@ def test_plain_loop_against_the_restatement_resynchronised(name, advance_time):
     mpc_period.plant_set_period(g, periods)
     free = g.clone()
     free.closed_loop_advance(0, runs, SUB, advance_time)
-    loops = [PeriodLoop(cfg, states[b], ees[b], NO_GAIT, SUB, advance_time, push_times[b], impulses[b], periods[b]) for b in range(B)]
+    loops = [RestatementLoop(cfg, states[b], ees[b], NO_GAIT, SUB, advance_time, push_times[b], impulses[b], periods[b]) for b in range(B)]
     seen = set()
     for r in range(1, runs + 1):
         g.set_warm_start_trajectory([l.o.trajectory_record(host) for l in loops])
@@ -206,55 +181,7 @@ def test_gait_loop_at_a_period_against_the_restatement_resynchronised(cfgname, p
     """test_closed_loop_with_gait_step_against_the_restatement_resynchronised at an MPC period: two identical instances, 11 runs, a push; kinds, ready
     flag, LP status and argmin compared at both line searches (checked on the CPU for exactly these inputs, tests/test_mpc_period_host.py: a ready
     gradient and a solved LP at runs 4 and 9, the two cheapest candidates more than 1e-4 apart at both line searches)"""
-    FREQ, RUNS = GAIT_FREQ, GAIT_RUNS
-    cfg = load_config(cfgname)
-    s0 = np.array(cfg['srb_init'], float)
-    g = host.BatchMPC.cold_start(cfg, [s0] * 2, EE_NOMINAL, mode=MODE)
-    g.plant_set_state(s0); g.plant_set_push(push_time, PUSH)
-    mpc_period.plant_set_period(g, period)
-    gait, roll = rollout(g, log=RUNS)
-    loop = PeriodLoop(cfg, s0, EE_NOMINAL, FREQ, SUB, 1, push_time, PUSH, period)
-    n_ls = n_argmin = 0
-    for r in range(1, RUNS + 1):
-        g.set_warm_start_trajectory([loop.o.trajectory_record(host)] * 2)
-        g.plant_set_state(loop.x)
-        out = loop.run()
-        roll.advance(r, 1, FREQ, SUB, True); g.synchronize()
-        if out['step'] is not None:
-            nv = int(gait.contact_times()[1][0].sum())
-            gait.set_step(out['step'][:nv])
-        st, err = g.status()
-        assert not err.any(), (r, err)
-        plant, tr = g.plant_state(), g.trajectory_states()
-        e_plant, e_tr = relerr(plant[0], out['plant']), relerr(tr[0], loop.o.states())
-        print('%s p = %g run %2d kind %d: plant %.1e states %.1e' % (cfgname, period, r, out['kind'], e_plant, e_tr))
-        assert np.array_equal(plant[0], plant[1]) and np.array_equal(tr[0], tr[1]), r
-        assert e_plant <= 1e-9, (r, e_plant)
-        assert e_tr < REL_TOL, (r, e_tr)
-        kg = g.knots(0)
-        same_bytes(np.frombuffer(bytes(g.get_trajectory(0, 1)), np.uint8), np.frombuffer(bytes(g.get_trajectory(1, 1)), np.uint8), 'run %d: the two instances' % r)
-        for e in range(4):
-            ko = loop.o.knots(e)
-            assert kg['nk'][e] == ko['K'] and np.array_equal(kg['times'][e, :ko['K']], ko['times']), (r, e)
-        rec = g.step_log(r - 1, 1)[0]
-        same_bytes(rec[0], rec[1], 'run %d: the records of the two instances' % r)
-        same_bytes(rec[:, 1], np.full(2, (r - 1) * period + period), 'run %d: init_time of the record' % r)
-        fields = gait_rollout.gait_fields_from_log(rec[0])
-        assert fields['kind'] == out['kind'], (r, fields, out['kind'])
-        if out['kind'] == GRADIENT:
-            assert fields['ready'] == int(out['ready']) == 1 and fields['lp_status'] == 0, (r, fields)
-        if out['kind'] == LINE_SEARCH:
-            n_ls += 1
-            imin, costs = roll.line_search_result()
-            assert imin[0] == imin[1] == fields['imin']
-            srt = np.sort(out['costs'])
-            print('   line search: device imin %d, restatement %d; its two cheapest candidates %.3e apart (relative)' %
-                  (imin[0], out['imin'], (srt[1] - srt[0]) / max(1.0, abs(srt[0]))))
-            if srt[1] - srt[0] > 1e-4 * max(1.0, abs(srt[0])):
-                n_argmin += 1
-                assert imin[0] == out['imin'], (r, imin[0], out['imin'], costs[0], out['costs'])
-    assert n_ls == 2 and n_argmin == 2, (n_ls, n_argmin)
-    gait.close(); g.close()
+    resync_gait_loop(cfgname, push_time, period)
 
 
 def test_gait_loop_one_call_against_single_calls_at_per_instance_periods():
@@ -286,20 +213,14 @@ def test_gait_loop_one_call_against_single_calls_at_per_instance_periods():
 def test_step_queues_at_mixed_periods_are_bitwise_the_per_instance_launch(monkeypatch):
     """CU count + 4 instances, periods cycling through [0.05, 0.025, 0.013], 6 steps: the time of an item is that of its instance"""
     cfg = load_config()
-    probe = host.BatchMPC(cfg, 1)
-    n_cu = probe.debug_launch_info()['n_cu']
-    probe.close()
+    n_cu = chip_cu_count()
     B, K = n_cu + 4, 6
     states, ees = instances(cfg, config_b_instance, B)
     periods = np.array([0.05, 0.025, 0.013])[np.arange(B) % 3]
     pt = np.full(B, 1e9); pt[::7] = 0.07
     imp = np.zeros((B, 6)); imp[::7, 0] = 1.5; imp[::7, 1] = -1.0
     res = {}
-    for no_queue in (False, True):
-        if no_queue:
-            monkeypatch.setenv('SRBM_NO_STEP_QUEUE', '1')
-        else:
-            monkeypatch.delenv('SRBM_NO_STEP_QUEUE', raising=False)
+    for no_queue in step_queues_on_and_off(monkeypatch):
         g = host.BatchMPC.cold_start(cfg, states, ees, mode=MODE)
         g.plant_set_state(states); g.plant_set_push(pt, imp)
         mpc_period.plant_set_period(g, periods)

@@ -17,6 +17,7 @@ import io
 import numpy as np
 import pytest
 
+from closed_loop_kit import chip_cu_count
 from gpu_kit import advance, assert_bitwise, same_bytes, snapshot
 from oracle_py import load_config
 from srbm_loader import host
@@ -162,11 +163,7 @@ def test_records_of_every_launch_form_equal_the_read_backs(base_b, chains, close
 def test_step_queues_write_the_records_of_the_chain():
     """a batch of n_cu + 8 instances, 4 closed-loop steps: the multi-step launch runs on the step queues (srbm_rti_queued_logged)"""
     cfg = load_config()
-    probe = cold_start(cfg, 2)
-    probe.rti_advance(0, 1); probe.synchronize()
-    n_cu = probe.debug_launch_info()['n_cu']
-    probe.close()
-    base = cold_start(cfg, n_cu + 8)
+    base = cold_start(cfg, chip_cu_count() + 8)
     ch = run_chain(base, True, 4, read_back=False)
     q = run_split(base, True, (4,))
     assert q['infos'][0]['kernel'] == 'srbm_rti_queued' and q['infos'][0]['queued'], q['infos']

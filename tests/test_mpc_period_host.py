@@ -1,6 +1,6 @@
 """The MPC period of the closed-loop protocols without a GPU (include/srbm_rti.h: srbm_plant_set_period; bilevel-gait-gen_amd/mpc_period.py):
 
-    a  PeriodLoop (tests/mpc_period_kit.py) at p = dt is RestatementLoop, bit for bit;
+    a  RestatementLoop (tests/closed_loop_kit.py) given p = dt is RestatementLoop given no period, bit for bit;
     b  the inputs of tests/test_gpu_mpc_period.py stay within their conditions on the restatement alone: every run Solved, more than one (n, m) per
        configuration, gradient ready and LP solved at runs 4 and 9, the two cheapest candidates of each line search more than 1e-4 apart;
     c  the two entries in the header and in the prototype table, and the wrapper's shape refusals before the library is called."""
@@ -11,8 +11,7 @@ import re
 import numpy as np
 import pytest
 
-from gait_rollout_kit import GRADIENT, LINE_SEARCH, RestatementLoop
-from mpc_period_kit import GAIT_CASES, GAIT_FREQ, GAIT_RUNS, NO_GAIT, PUSH, SUB, PeriodLoop, plain_case
+from closed_loop_kit import GAIT_CASES, GAIT_FREQ, GAIT_RUNS, GRADIENT, LINE_SEARCH, NO_GAIT, PUSH, SUB, RestatementLoop, plain_case
 from oracle_py import load_config
 from srbm_loader import ROOT, host, mpc_period
 from srbm_loader.workloads import EE_NOMINAL
@@ -25,7 +24,7 @@ def test_period_loop_at_the_node_step_is_the_restatement_loop_bitwise():
     cfg = load_config('a1_configuration')
     s0 = np.array(cfg['srb_init'], float)
     args = (cfg, s0, EE_NOMINAL, GAIT_FREQ, SUB, 1, 0.12, PUSH)
-    a, b = RestatementLoop(*args), PeriodLoop(*args, period=cfg['integrator_dt'])
+    a, b = RestatementLoop(*args), RestatementLoop(*args, period=cfg['integrator_dt'])
     kinds = []
     for r in range(1, GAIT_RUNS + 1):
         oa, ob = a.run(), b.run()
@@ -48,7 +47,7 @@ def test_plain_loop_inputs_stay_solved_and_change_size(name):
     for advance_time in adv:
         sizes = set()
         for b in range(len(periods)):
-            loop = PeriodLoop(cfg, states[b], ees[b], NO_GAIT, SUB, advance_time, push_times[b], impulses[b], periods[b])
+            loop = RestatementLoop(cfg, states[b], ees[b], NO_GAIT, SUB, advance_time, push_times[b], impulses[b], periods[b])
             for r in range(1, runs + 1):
                 out = loop.run()
                 assert out['kind'] == 0 and loop.o.stats()['status'] == 0, (name, advance_time, b, r, loop.o.stats()['status'])
@@ -62,7 +61,7 @@ def test_plain_loop_inputs_stay_solved_and_change_size(name):
 def test_gait_loop_inputs_have_ready_gradients_and_clear_line_searches(cfgname, push_time, period):
     cfg = load_config(cfgname)
     s0 = np.array(cfg['srb_init'], float)
-    loop = PeriodLoop(cfg, s0, EE_NOMINAL, GAIT_FREQ, SUB, 1, push_time, PUSH, period)
+    loop = RestatementLoop(cfg, s0, EE_NOMINAL, GAIT_FREQ, SUB, 1, push_time, PUSH, period)
     gaps = []
     for r in range(1, GAIT_RUNS + 1):
         out = loop.run()
