@@ -19,6 +19,7 @@
 #include "srbm_ik.hiph"
 #include "srbm_wbc.hiph"
 #include "srbm_tick.hiph"
+#include "srbm_rollout_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
 #include "../../include/srbm_rti.h"
@@ -86,6 +87,11 @@ struct srbm_batch {
     size_t stage_bytes = 0;
     double* d_log = nullptr;         // step log [log_cap][batch][SRBM_STEP_LOG_DOUBLES] (srbm_steplog.hiph), nullptr: logging off
     int log_cap = 0, log_used = 0;   // slots allocated; the cursor: slots written by the launches queued so far
+    // rollout summaries (srbm_rollout_summary.hiph): the log folded per instance, nullptr: off
+    double* d_sum = nullptr;         // [batch][SRBM_ROLLOUT_SUMMARY_DOUBLES]
+    double* d_sum_ref = nullptr;     // the references [batch][SRBM_ROLLOUT_REF_DOUBLES]
+    SrbmRolloutCriteria sum_crit{};  // the criteria, a kernel argument
+    std::vector<double> sum_init;    // host image of the summaries after a reset (the source of the asynchronous copy that resets them)
     // control tick (srbm_control_tick, srbm_tick.hiph): MPCController's member state for the batch, allocated by srbm_control_tick_reset
     double* d_tick_q = nullptr;              // q_des_ [batch][19]
     SrbmTickRec* d_tick_rec = nullptr;       // the targets of the tick under way [batch], between its two kernels
@@ -400,6 +406,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_state); (void)hipFree(h->d_time); (void)hipFree(h->d_ee);
     (void)hipFree(h->d_plant); (void)hipFree(h->d_push); (void)hipFree(h->d_period); (void)hipFree(h->d_dt);
     (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage); (void)hipFree(h->d_log);
+    (void)hipFree(h->d_sum); (void)hipFree(h->d_sum_ref);
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
@@ -864,6 +871,116 @@ int srbm_step_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out
     if (bytes == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(out_dev, src, bytes, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+// ---- rollout summaries (include/srbm_rti.h; csrc/srbm_rollout_summary.hiph) ----
+int srbm_rollout_summary_doubles(void) { return SRBM_ROLLOUT_SUMMARY_DOUBLES; }
+// criteria[8]: every entry finite, the reserved ones 0
+static int rollout_check_criteria(const char* fn, const double* criteria) {
+    for (int i = 0; i < SRBM_ROLLOUT_CRITERIA_DOUBLES; i++) {
+        if (!std::isfinite(criteria[i])) return fail(std::string(fn) + ": criterion " + std::to_string(i) + " is not finite");
+        if (i >= 6 && criteria[i] != 0.0) return fail(std::string(fn) + ": criterion " + std::to_string(i) + " is reserved and must be 0");
+    }
+    return 0;
+}
+static int rollout_enabled(const srbm_batch* h, const char* fn) {
+    if (!h) return fail(std::string(fn) + ": bad arguments");
+    if (!h->d_sum) return fail(std::string(fn) + ": no rollout summary is enabled on this batch (srbm_rollout_summary_enable)");
+    return 0;
+}
+int srbm_rollout_summary_reset(srbm_batch* h) {
+    if (rollout_enabled(h, "srbm_rollout_summary_reset")) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_sum, h->sum_init.data(), sizeof(double) * h->sum_init.size(), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+int srbm_rollout_summary_enable(srbm_batch* h, const double* criteria, const double* ref) {
+    if (!h) return fail("srbm_rollout_summary_enable: bad arguments");
+    if (criteria) {
+        if (!ref) return fail("srbm_rollout_summary_enable: criteria without references (ref[batch][6])");
+        if (rollout_check_criteria("srbm_rollout_summary_enable", criteria)) return -1;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_sum) HIPCHK(hipFree(h->d_sum));
+    h->d_sum = nullptr;
+    if (h->d_sum_ref) HIPCHK(hipFree(h->d_sum_ref));
+    h->d_sum_ref = nullptr;
+    if (!criteria) return 0;
+    const size_t B = h->batch;
+    std::memcpy(h->sum_crit.c, criteria, sizeof(h->sum_crit.c));
+    h->sum_init.resize(B * SRBM_ROLLOUT_SUMMARY_DOUBLES);
+    for (size_t b = 0; b < B; b++) srbm_rollout_summary_init(h->sum_init.data() + b * SRBM_ROLLOUT_SUMMARY_DOUBLES);
+    HIPCHK(hipMalloc(&h->d_sum_ref, sizeof(double) * SRBM_ROLLOUT_REF_DOUBLES * B));
+    HIPCHK(hipMemcpy(h->d_sum_ref, ref, sizeof(double) * SRBM_ROLLOUT_REF_DOUBLES * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&h->d_sum, sizeof(double) * SRBM_ROLLOUT_SUMMARY_DOUBLES * B));
+    return srbm_rollout_summary_reset(h);
+}
+int srbm_rollout_summary_fold(srbm_batch* h, int first_slot, int count) {
+    if (!h) return fail("srbm_rollout_summary_fold: bad arguments");
+    if (!h->d_log) return fail("srbm_rollout_summary_fold: no step log is enabled on this batch (srbm_step_log_enable)");
+    if (rollout_enabled(h, "srbm_rollout_summary_fold")) return -1;
+    if (first_slot < 0 || count < 0 || first_slot > h->log_used || count > h->log_used - first_slot)
+        return fail("srbm_rollout_summary_fold: slots [" + std::to_string(first_slot) + ", " + std::to_string((long long)first_slot + count) + ") are outside the " +
+                    std::to_string(h->log_used) + " steps logged");
+    if (count == 0) return 0;
+    if (use_batch(h)) return -1;
+    hipLaunchKernelGGL(srbm_k_rollout_fold, dim3(h->batch), dim3(64), 0, h->stream, h->dp, h->d_log, h->batch, first_slot, count, h->sum_crit, h->d_sum_ref,
+                       h->d_sum);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_rollout_summary_get(srbm_batch* h, int first, int count, double* out) {
+    if (rollout_enabled(h, "srbm_rollout_summary_get")) return -1;
+    if (!out) return fail("srbm_rollout_summary_get: bad arguments");
+    if (first < 0 || count < 0 || first > h->batch || count > h->batch - first)
+        return fail("srbm_rollout_summary_get: instances [" + std::to_string(first) + ", " + std::to_string((long long)first + count) + ") are outside the batch of " +
+                    std::to_string(h->batch));
+    if (count == 0) return 0;
+    return fetch(h, {{out, h->d_sum + (size_t)first * SRBM_ROLLOUT_SUMMARY_DOUBLES, sizeof(double) * SRBM_ROLLOUT_SUMMARY_DOUBLES * count}});
+}
+int srbm_rollout_summary_copy_dev(srbm_batch* h, double* out_dev) {
+    if (rollout_enabled(h, "srbm_rollout_summary_copy_dev")) return -1;
+    if (!out_dev) return fail("srbm_rollout_summary_copy_dev: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out_dev, h->d_sum, sizeof(double) * SRBM_ROLLOUT_SUMMARY_DOUBLES * (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+int srbm_rollout_study_dev(srbm_batch* h, const double* summaries_dev, int instances, double* study_dev) {
+    if (!h || !summaries_dev || !study_dev || instances < 0) return fail("srbm_rollout_study_dev: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(srbm_k_rollout_study, dim3(1), dim3(64), 0, h->stream, summaries_dev, instances, study_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_rollout_study(srbm_batch* h, double* study) {
+    if (rollout_enabled(h, "srbm_rollout_study")) return -1;
+    if (!study) return fail("srbm_rollout_study: bad arguments");
+    void* d = nullptr;
+    if (batch_scratch(h, sizeof(double) * SRBM_ROLLOUT_STUDY_DOUBLES, &d)) return -1;
+    if (srbm_rollout_study_dev(h, h->d_sum, h->batch, static_cast<double*>(d))) return -1;
+    return fetch(h, {{study, d, sizeof(double) * SRBM_ROLLOUT_STUDY_DOUBLES}});
+}
+// the same fold and the same reduction on the host: no GPU, no batch
+int srbm_rollout_fold_host(const double* log, int slots, int batch, int first_slot, int count, const double* criteria, const double* ref, const double* mu,
+                           double* summaries) {
+    if (!log || !criteria || !ref || !mu || !summaries || slots < 0 || batch < 1) return fail("srbm_rollout_fold_host: bad arguments");
+    if (rollout_check_criteria("srbm_rollout_fold_host", criteria)) return -1;
+    if (first_slot < 0 || count < 0 || first_slot > slots || count > slots - first_slot)
+        return fail("srbm_rollout_fold_host: slots [" + std::to_string(first_slot) + ", " + std::to_string((long long)first_slot + count) + ") are outside the " +
+                    std::to_string(slots) + " slots of the log");
+    for (int b = 0; b < batch; b++)
+        for (int s = first_slot; s < first_slot + count; s++)
+            srbm_rollout_fold_record(summaries + (size_t)b * SRBM_ROLLOUT_SUMMARY_DOUBLES, log + ((size_t)s * batch + b) * SRBM_STEP_LOG_DOUBLES, criteria,
+                                     ref + (size_t)b * SRBM_ROLLOUT_REF_DOUBLES, mu[b]);
+    return 0;
+}
+int srbm_rollout_study_host(const double* summaries, int instances, double* study) {
+    if (!summaries || !study || instances < 0) return fail("srbm_rollout_study_host: bad arguments");
+    double T[SRBM_ROLLOUT_STUDY_DOUBLES];
+    srbm_rollout_study_init(T);
+    for (int i = 0; i < instances; i++) srbm_rollout_study_add(T, summaries + (size_t)i * SRBM_ROLLOUT_SUMMARY_DOUBLES);
+    std::memcpy(study, T, sizeof(T));
     return 0;
 }
 int srbm_synchronize(srbm_batch* h) {
@@ -1408,7 +1525,9 @@ int srbm_rccl_comm_destroy(ncclComm_t comm) {
     if (r != ncclSuccess) return rccl_fail("ncclCommDestroy", r);
     return 0;
 }
-int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev) {
+// The two halves of an in-place all-gather of `count` doubles per rank on the batch's stream.  allgather_slot: RCCL bound, the communicator asked for
+// rank and world, *mine = this rank's slot of out_dev (the caller queues its doubles straight into it); allgather_run: ONE ncclAllGather.
+static int allgather_slot(const char* fn, srbm_batch* h, ncclComm_t comm, double* out_dev, size_t count, double** mine) {
     if (!h || !comm || !out_dev) return fail("bad arguments");
     RcclApi& A = rccl_api();
     if (!A.err.empty()) return fail(A.err);
@@ -1417,14 +1536,31 @@ int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev) {
     ncclResult_t r = A.CommUserRank(comm, &rank);
     if (r == ncclSuccess) r = A.CommCount(comm, &world);
     if (r != ncclSuccess) return rccl_fail("ncclCommUserRank / ncclCommCount", r);
-    if (rank < 0 || rank >= world) return fail("srbm_allgather_results: communicator reports an invalid rank");
-    const int ld = srbm_result_record_doubles(h->hp.N);
-    const size_t count = (size_t)h->batch * ld;
-    double* mine = out_dev + (size_t)rank * count;                  // in place: this rank's records go straight to their slot of the gathered array
-    if (srbm_pack_results_dev(h, mine, ld)) return -1;
-    r = A.AllGather(mine, out_dev, count, ncclDouble, comm, h->stream);
+    if (rank < 0 || rank >= world) return fail(std::string(fn) + ": communicator reports an invalid rank");
+    *mine = out_dev + (size_t)rank * count;
+    return 0;
+}
+static int allgather_run(srbm_batch* h, ncclComm_t comm, double* mine, double* out_dev, size_t count) {
+    const ncclResult_t r = rccl_api().AllGather(mine, out_dev, count, ncclDouble, comm, h->stream);
     if (r != ncclSuccess) return rccl_fail("ncclAllGather", r);
     return 0;
+}
+int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev) {
+    if (!h) return fail("bad arguments");
+    const int ld = srbm_result_record_doubles(h->hp.N);
+    const size_t count = (size_t)h->batch * ld;
+    double* mine = nullptr;
+    if (allgather_slot("srbm_allgather_results", h, comm, out_dev, count, &mine)) return -1;
+    if (srbm_pack_results_dev(h, mine, ld)) return -1;
+    return allgather_run(h, comm, mine, out_dev, count);
+}
+int srbm_rollout_allgather_dev(srbm_batch* h, ncclComm_t comm, double* out_dev) {
+    if (rollout_enabled(h, "srbm_rollout_allgather_dev")) return -1;
+    const size_t count = (size_t)h->batch * SRBM_ROLLOUT_SUMMARY_DOUBLES;
+    double* mine = nullptr;
+    if (allgather_slot("srbm_rollout_allgather_dev", h, comm, out_dev, count, &mine)) return -1;
+    if (srbm_rollout_summary_copy_dev(h, mine)) return -1;
+    return allgather_run(h, comm, mine, out_dev, count);
 }
 
 // ---------------- getters ----------------

@@ -166,6 +166,16 @@ int srbm_step_log_reset(srbm_batch*)
 int srbm_step_log_count(srbm_batch*, int*)
 int srbm_step_log_get(srbm_batch*, int, int, double*)
 int srbm_step_log_copy_dev(srbm_batch*, int, int, dev*)
+int srbm_rollout_summary_doubles()
+int srbm_rollout_summary_enable(srbm_batch*, double*, double*)
+int srbm_rollout_summary_reset(srbm_batch*)
+int srbm_rollout_summary_fold(srbm_batch*, int, int)
+int srbm_rollout_summary_get(srbm_batch*, int, int, double*)
+int srbm_rollout_summary_copy_dev(srbm_batch*, dev*)
+int srbm_rollout_study(srbm_batch*, double*)
+int srbm_rollout_study_dev(srbm_batch*, dev*, int, dev*)
+int srbm_rollout_fold_host(double*, int, int, int, int, double*, double*, double*, double*)
+int srbm_rollout_study_host(double*, int, double*)
 int srbm_sizeof_trajectory()
 int srbm_get_trajectory(srbm_batch*, int, int, srbm_trajectory*)
 int srbm_set_warm_start_trajectory(srbm_batch*, int, int, srbm_trajectory*)
@@ -229,6 +239,7 @@ int srbm_result_record_doubles(int)
 int srbm_pack_results_dev(srbm_batch*, dev*, int)
 int srbm_pack_results(srbm_batch*, double*, int)
 int srbm_allgather_results(srbm_batch*, ncclComm_t, dev*)
+int srbm_rollout_allgather_dev(srbm_batch*, ncclComm_t, dev*)
 int srbm_rccl_get_unique_id(void*)
 int srbm_rccl_comm_init_rank(srbm_batch*, int, int, void*, ncclComm_t*)
 int srbm_rccl_comm_destroy(ncclComm_t)

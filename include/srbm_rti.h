@@ -213,6 +213,99 @@ int srbm_step_log_count(srbm_batch* h, int* steps_logged);
 int srbm_step_log_get(srbm_batch* h, int first_slot, int count, double* out);
 int srbm_step_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev);
 
+/* ---- rollout summaries: the step log folded into one outcome record per instance, on the device ----
+ * What a disturbance-rejection study asks of a rollout -- did the instance fall, from when on was it back inside a band round its target, how far did it
+ * get, how close to the friction pyramid did the forces come, how many solves failed -- without copying the log to the host.  The fold is INCREMENTAL:
+ * log a chunk of steps, srbm_rollout_summary_fold, srbm_step_log_reset, repeat; a rollout of any length then needs a log of one chunk, and the
+ * summaries are bit for bit independent of the chunking (every sum is accumulated in slot order).  The entries only read the log: no result changes.
+ *
+ * criteria[8], one set for the batch (a record's state is log fields 17..29: position p 17..19, linear momentum h 20..22, quaternion xyzw 23..26,
+ * angular momentum L 27..29; ref[batch][6] = {p_ref[3], h_ref[3]} per instance).  Deviations are squared and the tilt is measured as
+ * u = 2 (qx qx + qy qy) = 1 - cos(tilt): the fold uses no division, square root or transcendental.
+ *     0  z_min        fallen if p_z < z_min
+ *     1  tilt_max     fallen if u > tilt_max
+ *     2  r2_settle    in band needs d2 = dx dx + dy dy <= r2_settle, dx = p_x - ref_x, dy likewise
+ *     3  dz_settle    in band needs |p_z - ref_z| <= dz_settle
+ *     4  tilt_settle  in band needs u <= tilt_settle
+ *     5  h2_settle    in band needs |h - h_ref|^2 <= h2_settle
+ *     6, 7            reserved, must be 0
+ * A record is in band when all four conditions hold.  A comparison with a NaN is false: a NaN never becomes a maximum or a minimum.
+ *
+ * One summary, SRBM_ROLLOUT_SUMMARY_DOUBLES doubles, integers stored as doubles.  k is the 0-based ordinal of a record among those folded since the
+ * last reset.  After a reset: counts and sums 0, every maximum -inf, every minimum +inf, every ordinal -1.  Where two records tie, the first keeps the
+ * ordinal.  mu is the instance's own friction coefficient.
+ *     0         records folded
+ *     1, 2      solve number (log field 0) of the first and of the last record
+ *     3, 4      init_time of the first and of the last record
+ *     5, 6      count of status != Solved; ordinal of the first such record
+ *     7         count of status > SolvedInacc
+ *     8         bitwise OR of the error bits (a field that holds no set of bits -- negative, 2^53 or more, NaN -- adds nothing)
+ *     9, 10     sum and max of the IPM iterations
+ *     11        sum of the cost (log field 8)
+ *     12        max dynamics defect
+ *     13        min alpha
+ *     14        max step norm
+ *     15, 16    min and max of p_z
+ *     17, 18    max d2 and the ordinal of its first occurrence
+ *     19, 20    max u and its ordinal
+ *     21        max |h - h_ref|^2
+ *     22        max |L|^2
+ *     23        ordinal of the first fallen record
+ *     24        ordinal of the last record NOT in band
+ *     25        count of in-band records
+ *     26        max f_z over the feet (log fields 44, 47, 50, 53)
+ *     27        min over records and feet with contact flag 1 of mu f_z - max(|f_x|, |f_y|)
+ *     28        count of records with a NaN among log fields 17..29 and 42..57: such a record is counted here and in 0..14 (and 38..42), and takes no
+ *               part in 15..37
+ *     29        count of records whose four contact flags differ from those of the record folded before it (among the records that take part)
+ *     30..33    the flags folded last: the carry; the first record sets it and counts no switch
+ *     34..37    per foot, count of records with flag 1
+ *     38, 39    count of gait runs of kind 1 and of kind 2 (log field 58)
+ *     40        sum of pred_red over the kind-1 records
+ *     41        count of kind-2 records with imin > 0
+ *     42        the winner's cost / n of the last kind-2 record
+ *     43..63    0
+ * Derived, stated here once: "settled from" = field 24 + 1; an instance is SETTLED if field 23 < 0 and field 24 < field 0 - 1 (it did not fall and its
+ * last record is in band); it has FALLEN if field 23 >= 0.
+ *
+ * One study record, SRBM_ROLLOUT_STUDY_DOUBLES doubles, of summaries[instances][64] taken in ascending instance order:
+ *     0         instances
+ *     1, 2      number fallen, number settled
+ *     3         number with summary field 7 > 0
+ *     4, 5      max (-1 where none is settled) and sum of "settled from" over the settled instances
+ *     6, 7      max of summary field 17, of summary field 19
+ *     8         min of summary field 27
+ *     9         sum of summary field 9
+ *     10        OR of summary field 8
+ *     11..15    0
+ *
+ * srbm_rollout_summary_enable: criteria[8] and ref[batch][6]; allocates the summaries and resets them; criteria == NULL disables them and frees the
+ * buffers.  srbm_rollout_summary_fold folds the log slots [first_slot, first_slot + count), which must lie in [0, steps_logged), asynchronously on the
+ * batch's stream like the advance entries: a logged launch, a fold and srbm_step_log_reset need no host synchronisation between them, the writes of the
+ * next launch are ordered behind the fold.  srbm_rollout_summary_get (synchronous): out[count][64] of instances [first, first + count);
+ * srbm_rollout_summary_copy_dev: all of them device to device on the stream, no synchronisation.  srbm_rollout_study (synchronous) reduces the batch's own
+ * summaries, srbm_rollout_study_dev (asynchronous) any device array of them -- the result of srbm_rollout_allgather_dev, which is srbm_allgather_results
+ * for summaries: in place, rank r's batch x 64 doubles to rows [r * batch, (r + 1) * batch) of out_dev[world * batch][64], one ncclAllGather.
+ * srbm_rollout_fold_host and srbm_rollout_study_host run the same fold of one record and the same reduction compiled for the host, on host arrays:
+ * log[slots][batch][64], mu[batch], summaries[batch][64] in and out (the caller sets them to the reset state above); no GPU, no batch.
+ * Refused before anything is queued, the batch and the summaries untouched, srbm_last_error naming the case: no step log enabled; no summary enabled; a
+ * slot or instance range outside what exists; NULL where it is not allowed; a criterion that is not finite; a reserved criterion other than 0.
+ * A clone has summaries off, as it has logging off. */
+#define SRBM_ROLLOUT_SUMMARY_DOUBLES 64
+#define SRBM_ROLLOUT_CRITERIA_DOUBLES 8
+#define SRBM_ROLLOUT_REF_DOUBLES 6
+#define SRBM_ROLLOUT_STUDY_DOUBLES 16
+int srbm_rollout_summary_doubles(void);                        /* SRBM_ROLLOUT_SUMMARY_DOUBLES; callable without a GPU */
+int srbm_rollout_summary_enable(srbm_batch* h, const double* criteria, const double* ref);
+int srbm_rollout_summary_reset(srbm_batch* h);
+int srbm_rollout_summary_fold(srbm_batch* h, int first_slot, int count);
+int srbm_rollout_summary_get(srbm_batch* h, int first, int count, double* out);
+int srbm_rollout_summary_copy_dev(srbm_batch* h, double* out_dev);
+int srbm_rollout_study(srbm_batch* h, double* study);
+int srbm_rollout_study_dev(srbm_batch* h, const double* summaries_dev, int instances, double* study_dev);
+int srbm_rollout_fold_host(const double* log, int slots, int batch, int first_slot, int count, const double* criteria, const double* ref, const double* mu, double* summaries);
+int srbm_rollout_study_host(const double* summaries, int instances, double* study);
+
 /* ---- mpc::Trajectory as a flat record (mpc/include/trajectory.h:20-175): what MPC::GetTrajectory returns by value and
  * MPC::SetWarmStartTrajectory takes.  Knot tables as srbm_get_knots: kind 0 lift-off, 1 touch-down, 2 stance-interior
  * (force node with value + slope/FORCE_MULT), 3 mid-swing; force[ee][coord][knot] = {value, slope/100} (used on kind-2
@@ -484,6 +577,8 @@ struct ncclComm;
 typedef struct ncclComm* ncclComm_t;               /* identical to the typedef in <rccl/rccl.h> */
 #define SRBM_RCCL_UNIQUE_ID_BYTES 128              /* sizeof(ncclUniqueId) */
 int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev);
+/* the same for the rollout summaries (see "rollout summaries" above): out_dev[world * batch][SRBM_ROLLOUT_SUMMARY_DOUBLES] */
+int srbm_rollout_allgather_dev(srbm_batch* h, ncclComm_t comm, double* out_dev);
 /* ncclGetUniqueId on one rank (bytes travel to the others by whatever the host uses for its rendezvous), ncclCommInitRank on the batch's device, ncclCommDestroy */
 int srbm_rccl_get_unique_id(void* id_bytes);
 int srbm_rccl_comm_init_rank(srbm_batch* h, int world, int rank, const void* id_bytes, ncclComm_t* comm_out);

@@ -1,5 +1,5 @@
 """Imports the modules of bilevel-gait-gen_amd/ (the directory name is not a Python identifier): `host` (ctypes binding of the C-ABI) and
-`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick` and `mpc_period` (the entries beside host.py)."""
+`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick`, `mpc_period` and `rollout_summary` (the entries beside host.py)."""
 import importlib.util
 import os
 import sys
@@ -25,3 +25,5 @@ control_tick = _load('srbm_control_tick', 'control_tick.py')
 sys.modules[__name__ + '.control_tick'] = control_tick
 mpc_period = _load('srbm_mpc_period', 'mpc_period.py')
 sys.modules[__name__ + '.mpc_period'] = mpc_period
+rollout_summary = _load('srbm_rollout_summary', 'rollout_summary.py')
+sys.modules[__name__ + '.rollout_summary'] = rollout_summary
