@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>          // types and prototypes only: RCCL is bound at run time (srbm_allgather_results), the library does not link it
 #include <dlfcn.h>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,7 @@
 #include "srbm_ik.hiph"
 #include "srbm_wbc.hiph"
 #include "srbm_tick.hiph"
+#include "srbm_wb_plant.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
@@ -95,6 +97,12 @@ struct srbm_batch {
     // control tick (srbm_control_tick, srbm_tick.hiph): MPCController's member state for the batch, allocated by srbm_control_tick_reset
     double* d_tick_q = nullptr;              // q_des_ [batch][19]
     SrbmTickRec* d_tick_rec = nullptr;       // the targets of the tick under way [batch], between its two kernels
+    // whole-controller rollouts (srbm_controller_advance, srbm_wb_plant.hiph), allocated by srbm_wb_plant_set_state: the plant's (q, v), the times of
+    // two ticks in turn and the outputs of the tick under way (WbBuf lays them out)
+    double* d_wb = nullptr;          // [WB_DOUBLES][batch]
+    int* d_wb_int = nullptr;         // [WB_INTS][batch]
+    double* d_tlog = nullptr;        // tick log [tlog_cap][batch][SRBM_TICK_LOG_DOUBLES], nullptr: logging off
+    int tlog_cap = 0, tlog_used = 0; // slots allocated; the cursor
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -408,6 +416,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_scratch); (void)hipFree(h->d_wbc); (void)hipHostFree(h->h_stage); (void)hipFree(h->d_log);
     (void)hipFree(h->d_sum); (void)hipFree(h->d_sum_ref);
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
+    (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -418,6 +427,24 @@ static int tick_alloc(srbm_batch* h) {
     const size_t B = h->batch;
     if (!h->d_tick_q) HIPCHK(hipMalloc(&h->d_tick_q, sizeof(double) * 19 * B));
     if (!h->d_tick_rec) HIPCHK(hipMalloc(&h->d_tick_rec, sizeof(SrbmTickRec) * B));
+    return 0;
+}
+// the buffers of the whole-controller rollout (srbm_wb_plant_set_state, srbm_batch_clone): per instance q[19], v[18], time[2] (ticks k and k + 1 in
+// turn), control[36], qp_sol[30], state[13], ee[12]; status[2], contact[4]
+enum { WB_DOUBLES = 19 + 18 + 2 + 36 + WBC_NMAX + 13 + 12, WB_INTS = 2 + 4 };
+struct WbBuf { double *q, *v, *time, *control, *sol, *state, *ee; int *status, *contact; };
+static WbBuf wb_buf(const srbm_batch* h) {
+    const size_t B = h->batch;
+    WbBuf w;
+    w.q = h->d_wb; w.v = w.q + 19 * B; w.time = w.v + 18 * B; w.control = w.time + 2 * B; w.sol = w.control + 36 * B; w.state = w.sol + WBC_NMAX * B;
+    w.ee = w.state + 13 * B;
+    w.status = h->d_wb_int; w.contact = w.status + 2 * B;
+    return w;
+}
+static int wb_alloc(srbm_batch* h) {
+    const size_t B = h->batch;
+    if (!h->d_wb) HIPCHK(hipMalloc(&h->d_wb, sizeof(double) * WB_DOUBLES * B));
+    if (!h->d_wb_int) HIPCHK(hipMalloc(&h->d_wb_int, sizeof(int) * WB_INTS * B));
     return 0;
 }
 static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
@@ -557,6 +584,8 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     if (ok && src->d_wbc) ok = hipMalloc(&h->d_wbc, sizeof(SrbmWbcParams)) == hipSuccess && cp(h->d_wbc, src->d_wbc, sizeof(SrbmWbcParams));      // (a clone carries the complete state)
     // (the control tick's q_des_ goes along)
     if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
+    // (... and the whole-body plant's (q, v); the tick log, like the step log, stays off)
+    if (ok && src->d_wb) ok = wb_alloc(h) == 0 && cp(h->d_wb, src->d_wb, sizeof(double) * (19 + 18) * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2117,6 +2146,125 @@ int srbm_control_tick(srbm_batch* h, const double* q, const double* v, const dou
     if (contact) memcpy(contact, c.host(ocon), ocon.bytes());
     if (state) memcpy(state, c.host(ox), ox.bytes());
     if (ee) memcpy(ee, c.host(oe), oe.bytes());
+    return 0;
+}
+
+// ---------------- whole-controller rollouts: MPC updates, control ticks, whole-body plant (srbm_wb_plant.hiph) ----------------
+int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
+    if (!h || !q || !v) return fail("srbm_wb_plant_set_state: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (wb_alloc(h)) return -1;
+    const WbBuf w = wb_buf(h);
+    HIPCHK(hipMemcpyAsync(w.q, q, sizeof(double) * 19 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(w.v, v, sizeof(double) * 18 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
+    if (!h) return fail("srbm_wb_plant_get_state: bad arguments");
+    if (!h->d_wb) return fail("the whole-body plant state has not been set (srbm_wb_plant_set_state)");
+    const WbBuf w = wb_buf(h);
+    return fetch(h, {{q, w.q, sizeof(double) * 19 * (size_t)h->batch}, {v, w.v, sizeof(double) * 18 * (size_t)h->batch}});
+}
+// the plant step of tick `tick` on the batch's stream; lg: the record of the tick, nullptr: the unlogged kernel
+static int launch_wb_plant(srbm_batch* h, int tick, double tick_dt, double* q, double* v, const double* qp_sol, const int* status, double* time_next,
+                           const SrbmTickLogArgs* lg) {
+    const double* push = h->push_set ? h->d_push : nullptr;
+    if (lg) hipLaunchKernelGGL((srbm_k_wb_plant_step<true>), dim3(h->batch), dim3(64), 0, h->stream, h->dp, tick, tick_dt, push, q, v, qp_sol, status, time_next, *lg);
+    else hipLaunchKernelGGL((srbm_k_wb_plant_step<false>), dim3(h->batch), dim3(64), 0, h->stream, h->dp, tick, tick_dt, push, q, v, qp_sol, status, time_next,
+                            SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0});
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_plant_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* qp_sol_dev, const int* status_dev) {
+    if (!h || !q_dev || !v_dev || !qp_sol_dev || !status_dev) return fail("srbm_wb_plant_step_dev: bad arguments");
+    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_plant_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
+    if (use_batch(h)) return -1;
+    return launch_wb_plant(h, tick, tick_dt, q_dev, v_dev, qp_sol_dev, status_dev, nullptr, nullptr);
+}
+int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt) {
+    const std::string fn = "srbm_controller_advance";
+    if (!h) return fail(fn + ": bad arguments (NULL handle)");
+    if (!h->d_wb) return fail(fn + ": the whole-body plant state has not been set (srbm_wb_plant_set_state)");
+    if (tick_usable(h)) return -1;
+    if (first_tick < 0 || ticks < 0 || ticks > INT_MAX - first_tick) return fail(fn + ": first_tick >= 0 and ticks >= 0 are required");
+    if (ticks_per_update < 1) return fail(fn + ": ticks_per_update >= 1 is required");
+    if (!std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(fn + ": a finite tick_dt > 0 is required");
+    const double period = ticks_per_update * tick_dt, horizon = h->hp.N * h->hp.dt;
+    if (!(period < horizon)) {
+        char v[64]; std::snprintf(v, sizeof v, "%.17g", period);
+        return fail(fn + ": the MPC period ticks_per_update * tick_dt is " + v + ": a period below num_nodes * dt = " + std::to_string(horizon) +
+                    " is required (beyond it the ticks would read past the trajectory)");
+    }
+    // an MPC update follows tick k > 0 with k % ticks_per_update == 0
+    auto updates_before = [&](long long k) { return k <= 0 ? 0LL : (k - 1) / ticks_per_update; };          // such k in [0, k)
+    const int updates = (int)(updates_before((long long)first_tick + ticks) - updates_before(first_tick));
+    if (h->d_tlog && ticks > h->tlog_cap - h->tlog_used)
+        return fail(fn + ": the tick log has room for " + std::to_string(h->tlog_cap - h->tlog_used) + " more ticks (" + std::to_string(h->tlog_used) + " of " +
+                    std::to_string(h->tlog_cap) + " logged), the call asks for " + std::to_string(ticks) + " (srbm_tick_log_reset, or srbm_tick_log_enable with more ticks)");
+    if (log_room(h, fn.c_str(), updates)) return -1;
+    if (use_batch(h)) return -1;
+    if (ticks == 0) return 0;
+    const size_t B = h->batch;
+    const WbBuf w = wb_buf(h);
+    hipLaunchKernelGGL(srbm_k_wb_tick_time, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, w.time + (first_tick & 1) * B, h->batch, first_tick, tick_dt);
+    for (int k = first_tick; k < first_tick + ticks; k++) {
+        double* const time = w.time + (k & 1) * B;
+        const bool update = k > 0 && k % ticks_per_update == 0;
+        if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
+        const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
+        if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
+        if (h->d_tlog) h->tlog_used++;
+        // the hand-off of mpc_controller.cpp:142-156: the state and foot positions of THIS tick to the solve, the new trajectories in force from tick k + 1
+        if (update && srbm_get_real_time_update_dev(h, w.state, time, w.ee)) return -1;
+    }
+    return 0;
+}
+// ---- the tick log (include/srbm_rti.h; the record is written by srbm_k_wb_plant_step<true>) ----
+int srbm_tick_log_record_doubles(void) { return SRBM_TICK_LOG_DOUBLES; }
+int srbm_tick_log_enable(srbm_batch* h, int max_ticks) {
+    if (!h || max_ticks < 0) return fail("srbm_tick_log_enable: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_tlog) HIPCHK(hipFree(h->d_tlog));
+    h->d_tlog = nullptr; h->tlog_cap = 0; h->tlog_used = 0;
+    if (max_ticks == 0) return 0;
+    HIPCHK(hipMalloc(&h->d_tlog, sizeof(double) * SRBM_TICK_LOG_DOUBLES * (size_t)h->batch * (size_t)max_ticks));
+    h->tlog_cap = max_ticks;
+    return 0;
+}
+int srbm_tick_log_reset(srbm_batch* h) {
+    if (!h) return fail("srbm_tick_log_reset: bad arguments");
+    h->tlog_used = 0;
+    return 0;
+}
+int srbm_tick_log_count(srbm_batch* h, int* ticks_logged) {
+    if (!h || !ticks_logged) return fail("srbm_tick_log_count: bad arguments");
+    *ticks_logged = h->tlog_used;
+    return 0;
+}
+static int tick_log_range(const srbm_batch* h, const char* fn, int first_slot, int count, const void* out, const double** src, size_t* bytes) {
+    if (!h || !out) return fail(std::string(fn) + ": bad arguments");
+    if (!h->d_tlog) return fail(std::string(fn) + ": no tick log is enabled on this batch (srbm_tick_log_enable)");
+    if (first_slot < 0 || count < 0 || first_slot > h->tlog_used || count > h->tlog_used - first_slot)
+        return fail(std::string(fn) + ": slots [" + std::to_string(first_slot) + ", " + std::to_string((long long)first_slot + count) + ") are outside the " +
+                    std::to_string(h->tlog_used) + " ticks logged");
+    const size_t rec = (size_t)SRBM_TICK_LOG_DOUBLES * h->batch;
+    *src = h->d_tlog + rec * first_slot;
+    *bytes = sizeof(double) * rec * count;
+    return 0;
+}
+int srbm_tick_log_get(srbm_batch* h, int first_slot, int count, double* out) {
+    const double* src = nullptr; size_t bytes = 0;
+    if (tick_log_range(h, "srbm_tick_log_get", first_slot, count, out, &src, &bytes)) return -1;
+    if (bytes == 0) return 0;
+    return fetch(h, {{out, src, bytes}});
+}
+int srbm_tick_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev) {
+    const double* src = nullptr; size_t bytes = 0;
+    if (tick_log_range(h, "srbm_tick_log_copy_dev", first_slot, count, out_dev, &src, &bytes)) return -1;
+    if (bytes == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out_dev, src, bytes, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 

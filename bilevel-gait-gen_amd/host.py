@@ -222,6 +222,16 @@ int srbm_qp_control_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, d
 int srbm_control_tick_reset(srbm_batch*, double*)
 int srbm_control_tick(srbm_batch*, double*, double*, double*, double*, double*, int*, double*, double*, int*, double*, double*)
 int srbm_control_tick_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_wb_plant_set_state(srbm_batch*, double*, double*)
+int srbm_wb_plant_get_state(srbm_batch*, double*, double*)
+int srbm_wb_plant_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*)
+int srbm_controller_advance(srbm_batch*, int, int, int, double)
+int srbm_tick_log_record_doubles()
+int srbm_tick_log_enable(srbm_batch*, int)
+int srbm_tick_log_reset(srbm_batch*)
+int srbm_tick_log_count(srbm_batch*, int*)
+int srbm_tick_log_get(srbm_batch*, int, int, double*)
+int srbm_tick_log_copy_dev(srbm_batch*, int, int, dev*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

@@ -516,6 +516,69 @@ int srbm_control_tick(srbm_batch* h, const double* q, const double* v, const dou
 int srbm_control_tick_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* time_dev, double* control_dev, double* qp_sol_dev, int* status_dev,
                           double* q_des_dev, double* v_des_dev, int* contact_dev, double* state_dev, double* ee_dev);
 
+/* ---- whole-controller rollouts: MPC updates, control ticks and a whole-body plant, device-resident ----
+ * The reference's top-level program (test/simulation_mpc.cpp:186-215) runs MPCController::ComputeControlAction at the control rate, an MPC update
+ * whenever a newer state sample is there, and a whole-body simulation (MuJoCo: out of scope) in between.  srbm_controller_advance runs that loop for
+ * every instance with a plant that needs no contact solver.  The whole-body QP (controllers/qp_control.cpp) holds the six floating-base rows of
+ * M a + C v + g = S' tau + Js' F as equalities (:181-196), the stance-foot rows Js a = -Jsdot v as equalities (:198-222), and the joint rows of the
+ * same equation, which define the torques it returns (:224-240, RecoverControlInputs :404-415): (a, F) of a solved QP IS the forward dynamics of the
+ * whole-body model under the returned feed-forward torques with the planned stance feet held by the contact forces.  The plant integrates that a.
+ * What the plant is NOT: it has no ground and no collision -- a foot is in stance when the plan says so, wherever it is (hence the foot heights in
+ * the tick log); it does not model the joint PD loop the reference's robot adds to the feed-forward torque; and there is no
+ * AdjustForCurrentContacts, for the same reason as in the other closed loops.
+ *
+ * The plant step of tick k, period h = tick_dt, t_k = k * h (one rounded product, never accumulated):
+ *     a   = qp_sol[0..18) of the tick; 0 (the plant coasts) for exactly the instances to which the tick returned a zero control action
+ *           (QP status > 1: not solved, or targets status 2)
+ *     v+  = v + h a, then, if t_k < push_time <= t_k + h for the instance's push {time, impulse[6]} (srbm_plant_set_push):
+ *           v+[0..3) += impulse[0..3) / mass, v+[3..6) += Ir^-1 impulse[3..6) with the instance's own mass and inertia, so that
+ *           ReconstructState sees the momentum move by the impulse
+ *     q+  = pinocchio::integrate(q, v+, h)
+ * srbm_wb_plant_set_state: q[batch][19], v[batch][18]; allocates what the batch holds for the loop.  srbm_wb_plant_get_state: either pointer may be
+ * NULL.  srbm_wb_plant_step_dev: the same kernel on the caller's device arrays q_dev[batch][19], v_dev[batch][18], in place, from qp_sol_dev[batch][30]
+ * and status_dev[batch][2] as srbm_control_tick_dev returned them; one launch on the batch's stream, no copy, no synchronisation; never logs (a
+ * host can drive the loop itself and be compared bit for bit).  srbm_batch_clone carries the plant's (q, v). */
+int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v);
+int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v);
+int srbm_wb_plant_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* qp_sol_dev, const int* status_dev);
+/* Asynchronous on the batch's stream.  For k = first_tick .. first_tick + ticks - 1, in order:
+ *   1. srbm_control_tick_dev on the batch's (q, v) at t_k, on the current trajectories;
+ *   2. the plant step, and the record of the tick if a tick log is enabled;
+ *   3. if k > 0 and k % ticks_per_update == 0: srbm_get_real_time_update_dev on the state and ee that step 1 wrote, at init_time = t_k.  The new
+ *      trajectories are in force from tick k + 1 on: ComputeControlAction publishes (mpc_controller.cpp:142-156), the MPC thread picks up, with zero
+ *      computation delay.  With a step log enabled that solve writes its usual record, so srbm_rollout_summary_fold works on such a rollout unchanged.
+ * The MPC period ticks_per_update * tick_dt is batch-wide and may lie off the node grid (as srbm_plant_set_period established).
+ * Refused with a message, nothing launched, plant, trajectories, q_des and both log cursors untouched: no plant state set; no leg kinematics; no
+ * whole-body model; no srbm_control_tick_reset; first_tick < 0; ticks < 0; ticks_per_update < 1; tick_dt not finite or <= 0;
+ * ticks_per_update * tick_dt >= num_nodes * dt; a tick log or a step log without room. */
+int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt);
+/* The tick log: log[slot][batch][SRBM_TICK_LOG_DOUBLES], one record per tick and instance, written by the plant-step kernel (the unlogged kernel
+ * carries none of it); integers stored as doubles.  Every field is an output of THIS tick, read before the plant step: a record is, bit for bit,
+ * what a one-tick call returns.
+ *     index     content
+ *     0, 1      tick index k, time t_k
+ *     2         targets status
+ *     3, 4      QP status, QP iterations
+ *     5         flags: bit 0 the push was applied in this tick, bit 1 an MPC update followed this tick, bit 2 the plant coasted
+ *     6..12     base position and quaternion of the measured q
+ *     13..18    base twist of the measured v
+ *     19..30    torques (control[24..36))
+ *     31..42    contact forces per foot [4][3], unstacked from qp_sol, zero for a foot not in contact
+ *     43..46    desired contacts [4]
+ *     47..50    foot heights (ee[.][2]) [4]
+ *     51..56    base acceleration a[0..6)
+ *     57..63    0
+ * The entries have the semantics of their srbm_step_log_* counterparts: srbm_tick_log_enable allocates max_ticks x batch records and sets the cursor to
+ * 0 (0 disables and frees); capacity is checked before anything is launched; get (host, synchronous) and copy_dev (on the stream) fail for a slot
+ * range outside [0, ticks_logged) and when no log is enabled.  A clone has logging off. */
+#define SRBM_TICK_LOG_DOUBLES 64
+int srbm_tick_log_record_doubles(void);                          /* SRBM_TICK_LOG_DOUBLES; callable without a GPU */
+int srbm_tick_log_enable(srbm_batch* h, int max_ticks);
+int srbm_tick_log_reset(srbm_batch* h);                          /* cursor 0, buffer kept */
+int srbm_tick_log_count(srbm_batch* h, int* ticks_logged);
+int srbm_tick_log_get(srbm_batch* h, int first_slot, int count, double* out);
+int srbm_tick_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev);
+
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */
 int srbm_get_sizes(srbm_batch* h, int* sizes);

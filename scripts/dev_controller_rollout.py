@@ -1,0 +1,105 @@
+"""What a whole-controller rollout costs (srbm_controller_advance), by the protocol of dev_control_tick.py:
+256 Config-B instances after the cold start, 200 ticks of 1 ms, an MPC update every 50 ticks, the variants in turn on fresh clones, three runs each;
+medians and spreads.
+  (a) entry      srbm_controller_advance, all ticks in one call (without and with a tick log: the difference is what the logged kernel adds)
+  (b) chain      the loop driven from the host: srbm_control_tick_dev, srbm_wb_plant_step_dev, srbm_get_real_time_update_dev
+  (c) plant      the plant-step kernel alone (srbm_wb_plant_step_dev, unlogged), 200 launches on the outputs of one tick
+Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
+Prints one JSON line."""
+import json
+import os
+import signal
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from srbm_loader import host
+from srbm_loader.control_tick import ControlTick
+from srbm_loader.controller_rollout import ControllerRollout, TICK_LOG_FIELDS as F, FLAG_COAST
+from srbm_loader.workloads import config_b_instance, instances
+
+B, TICKS, TPU, DT, LIMIT_S = 256, 200, 50, 1e-3, 60.0
+RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+
+
+def main():
+    import torch
+    signal.signal(signal.SIGALRM, signal.SIG_DFL)
+    cfg = host.load_config('a1_configuration')
+    states, ees = instances(cfg, config_b_instance, B)
+    signal.setitimer(signal.ITIMER_REAL, 300.0)
+    base = host.BatchMPC.cold_start(cfg, states, ees)
+    q_init = np.tile(np.array(cfg['init_config'], float), (B, 1))
+    q0, v0, _, st = base.clone().get_targets_from_traj(0.0, q_init)          # the plant starts on the targets of tick 0
+    res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': []}
+    info = {}
+    f64 = dict(dtype=torch.float64, device='cuda')
+
+    def fresh(tick_log=0):
+        g = base.clone()
+        R = ControllerRollout(g)
+        R.reset(q_init); R.set_state(q0, v0)
+        if tick_log:
+            R.tick_log_enable(tick_log)
+        return g, R
+
+    def timed(g, fn):
+        g.synchronize()
+        tb = time.perf_counter()
+        fn()
+        g.synchronize()
+        return 1e3 * (time.perf_counter() - tb) / TICKS
+
+    for run in range(RUNS):
+        for name, tl in (('entry', 0), ('entry_logged', TICKS + 3)):
+            g, R = fresh(tl)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)                                          # warm-up: three ticks
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            if tl:
+                log = R.tick_log()
+                info['coasted_ticks'] = int(((log[:, :, F['flags']].astype(int) & FLAG_COAST) != 0).sum())
+                info['targets_not_ok'] = int((log[:, :, F['targets_status']] != 0).sum())
+                info['base_height_range'] = [float(log[:, :, 8].min()), float(log[:, :, 8].max())]
+            info['finite_' + name] = bool(np.all(np.isfinite(R.state()[0])))
+        # (b) the same loop from the host, on torch's buffers, on the batch's stream
+        g, R = fresh()
+        T = ControlTick(g)
+        with torch.cuda.stream(torch.cuda.ExternalStream(g.stream())):
+            q_d, v_d, t_d = torch.tensor(q0, **f64), torch.tensor(v0, **f64), torch.zeros(B, **f64)
+            ctl_d, sol_d, x_d, ee_d = torch.zeros((B, 36), **f64), torch.zeros((B, 30), **f64), torch.zeros((B, 13), **f64), torch.zeros((B, 12), **f64)
+            st_d, con_d = torch.zeros((B, 2), dtype=torch.int32, device='cuda'), torch.zeros((B, 4), dtype=torch.int32, device='cuda')
+
+            def chain(first, n):
+                for k in range(first, first + n):
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    t_d.fill_(k * DT)
+                    T.tick_dev(q_d.data_ptr(), v_d.data_ptr(), t_d.data_ptr(), ctl_d.data_ptr(), sol_d.data_ptr(), st_d.data_ptr(), None, None,
+                               con_d.data_ptr(), x_d.data_ptr(), ee_d.data_ptr())
+                    R.plant_step_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), sol_d.data_ptr(), st_d.data_ptr())
+                    if k > 0 and k % TPU == 0:
+                        g.get_real_time_update_dev(x_d.data_ptr(), t_d.data_ptr(), ee_d.data_ptr())
+            chain(0, 3)
+            res['chain'].append(timed(g, lambda: chain(3, TICKS)))
+            info['finite_chain'] = bool(torch.isfinite(q_d).all().item())
+
+            # (c) the plant-step kernel alone
+            def plant():
+                for k in range(TICKS):
+                    R.plant_step_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), sol_d.data_ptr(), st_d.data_ptr())
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            plant()
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res['plant'].append(timed(g, plant))
+    signal.setitimer(signal.ITIMER_REAL, 0)
+    med = {k: float(np.median(v)) for k, v in res.items()}
+    print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
+                          spread_ms={k: float(max(v) - min(v)) for k, v in res.items()}, **info)))
+
+
+if __name__ == '__main__':
+    main()

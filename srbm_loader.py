@@ -27,3 +27,4 @@ mpc_period = _load('srbm_mpc_period', 'mpc_period.py')
 sys.modules[__name__ + '.mpc_period'] = mpc_period
 rollout_summary = _load('srbm_rollout_summary', 'rollout_summary.py')
 sys.modules[__name__ + '.rollout_summary'] = rollout_summary
+controller_rollout = sys.modules[__name__ + '.controller_rollout'] = _load('srbm_controller_rollout', 'controller_rollout.py')
