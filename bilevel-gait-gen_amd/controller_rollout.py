@@ -1,14 +1,16 @@
 """Whole-controller rollouts (include/srbm_rti.h: srbm_controller_advance, srbm_wb_plant_*, srbm_tick_log_*): the loop of the reference's top-level
 program (test/simulation_mpc.cpp:186-215) for every instance of a host.BatchMPC -- MPCController::ComputeControlAction every tick, an MPC update
-every `ticks_per_update` ticks, and between them a whole-body plant that integrates the accelerations of the whole-body QP (it has no ground, no
-joint PD loop and no AdjustForCurrentContacts: the header says what that means).  A module of its own beside host.py, as control_tick.py and
-mpc_period.py are: it calls through the library `host.declare` has typed, and tests/test_abi_prototypes.py keeps the method list of host.BatchMPC
-as it stands.
+every `ticks_per_update` ticks, and between them a whole-body plant: by default the one that integrates the accelerations of the whole-body QP
+(it has no ground, no joint PD loop and no AdjustForCurrentContacts: the header says what that means), or, after set_plant(1, ...), the
+torque-driven one -- the constrained forward dynamics of the plant's own bodies under the returned torques, the joint PD loop and the torque limits.
+A module of its own beside host.py, as control_tick.py and mpc_period.py are: it calls through the library `host.declare` has typed, and
+tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands.
 
     R = ControllerRollout(mpc)            mpc: a BatchMPC with leg kinematics and a whole-body model, after its cold start
     R.reset(q_des)                        the IK guess of the first tick (srbm_control_tick_reset)
     R.set_state(q, v)                     the plant's (q, v)
     mpc.plant_set_push(time, impulse)     optional: one push per instance
+    R.set_plant(1, kp, kd, limit, 4)      optional: the torque-driven plant, 4 sub-steps per tick; R.set_plant_bodies(...): its own bodies
     R.tick_log_enable(200)                optional: one record per tick and instance
     R.advance(0, 200, 50, 1e-3)           200 ticks of 1 ms, an MPC update every 50; asynchronous
     q, v = R.state(); log = R.tick_log()"""
@@ -17,12 +19,16 @@ import ctypes as C
 import numpy as np
 
 _dp = C.POINTER(C.c_double)
+_ip = C.POINTER(C.c_int)
 
 TICK_LOG_DOUBLES = 64
-# one record of the tick log: field name -> slice of its TICK_LOG_DOUBLES doubles (include/srbm_rti.h); [57, 64) is 0
+# one record of the tick log: field name -> slice of its TICK_LOG_DOUBLES doubles (include/srbm_rti.h); [57, 64) is 0 with the QP-acceleration plant
 TICK_LOG_FIELDS = dict(tick=0, time=1, targets_status=2, qp_status=3, qp_iters=4, flags=5, base_pose=slice(6, 13), base_twist=slice(13, 19),
                        torques=slice(19, 31), contact_forces=slice(31, 43), contact=slice(43, 47), foot_heights=slice(47, 51), base_accel=slice(51, 57))
-FLAG_PUSH, FLAG_UPDATE, FLAG_COAST = 1, 2, 4
+# ... and what the torque-driven plant writes into [57, 63) (field 63 stays 0): 58..62 are of the last sub-step of the tick
+TORQUE_PLANT_LOG_FIELDS = dict(plant_kind=57, clamped_joints=58, torque_deviation=59, min_stance_fz=60, accel_mismatch=61, force_mismatch=62)
+FLAG_PUSH, FLAG_UPDATE, FLAG_COAST, FLAG_BREAKDOWN = 1, 2, 4, 8
+PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
 
 
 def _d(a):
@@ -59,6 +65,41 @@ class ControllerRollout:
         """the plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from qp_sol[batch][30], status[batch][2] of
         control_tick_dev; asynchronous, never logs"""
         self.mpc._chk(self.L.srbm_wb_plant_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, qp_sol, status))
+
+    # ---- the torque-driven plant ----
+    def set_plant(self, kind, kp=None, kd=None, torque_limit=None, substeps=1):
+        """the plant `advance` launches: PLANT_QP_ACCELERATION (the default) or PLANT_TORQUE_DRIVEN.  kp, kd, torque_limit (one [12] or [batch][12])
+        are the robot's actuator gains and limits, substeps the sub-steps per tick: set when one of the three is given (kp, kd None: 0;
+        torque_limit None: no limit), else left as they are"""
+        m = self.mpc
+        if kp is not None or kd is not None or torque_limit is not None:
+            lim = np.full(12, np.inf) if torque_limit is None else torque_limit
+            m._chk(self.L.srbm_wb_plant_set_actuators(m.h, _d(m._bcast(np.zeros(12) if kp is None else kp, 12)),
+                                                      _d(m._bcast(np.zeros(12) if kd is None else kd, 12)), _d(m._bcast(lim, 12)), int(substeps)))
+        m._chk(self.L.srbm_wb_plant_set_kind(m.h, int(kind)))
+
+    def set_plant_bodies(self, mass, com, inertia):
+        """the plant's own bodies: mass [13] or [batch][13], com [13][3] or [batch][13][3], inertia [13][3][3] or [batch][13][3][3]"""
+        m = self.mpc
+        m._chk(self.L.srbm_wb_plant_set_bodies_each(m.h, _d(m._bcast(mass, 13)), _d(m._bcast(com, 39)), _d(m._bcast(inertia, 117))))
+
+    def forward_dynamics(self, q, v, tau, contact):
+        """the constrained forward dynamics alone on the plant's bodies -> sol[batch][30] (a, then F stacked in foot order), status[batch]"""
+        m = self.mpc
+        con = np.ascontiguousarray(np.broadcast_to(np.asarray(contact, dtype=np.int32), (m.batch, 4)))
+        sol, st = np.zeros((m.batch, 30)), np.zeros(m.batch, np.int32)
+        m._chk(self.L.srbm_wb_forward_dynamics(m.h, _d(m._bcast(q, 19)), _d(m._bcast(v, 18)), _d(m._bcast(tau, 12)), con.ctypes.data_as(_ip), _d(sol),
+                                               st.ctypes.data_as(_ip)))
+        return sol, st
+
+    def forward_dynamics_dev(self, q, v, tau, contact, sol, status):
+        """the same on device pointers (ints); asynchronous"""
+        self.mpc._chk(self.L.srbm_wb_forward_dynamics_dev(self.mpc.h, q, v, tau, contact, sol, status))
+
+    def fd_step_dev(self, tick, tick_dt, q, v, control, contact, status, sol=None):
+        """the torque-driven plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from control[batch][36],
+        contact[batch][4], status[batch][2] of control_tick_dev; sol: None or [batch][30] <- (a, F) of the last sub-step; asynchronous, never logs"""
+        self.mpc._chk(self.L.srbm_wb_fd_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, control, contact, status, sol))
 
     # ---- the tick log ----
     def tick_log_enable(self, max_ticks):

@@ -21,6 +21,7 @@
 #include "srbm_wbc.hiph"
 #include "srbm_tick.hiph"
 #include "srbm_wb_plant.hiph"
+#include "srbm_wb_fd.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
@@ -103,6 +104,11 @@ struct srbm_batch {
     int* d_wb_int = nullptr;         // [WB_INTS][batch]
     double* d_tlog = nullptr;        // tick log [tlog_cap][batch][SRBM_TICK_LOG_DOUBLES], nullptr: logging off
     int tlog_cap = 0, tlog_used = 0; // slots allocated; the cursor
+    // the torque-driven plant (srbm_wb_fd.hiph): the kind srbm_controller_advance launches, the actuators and the plant's own bodies
+    int fd_kind = 0;                 // 0: the QP-acceleration plant, 1: the torque-driven plant (srbm_wb_plant_set_kind)
+    int fd_substeps = 1;
+    double* d_fd_act = nullptr;      // [batch][WBFD_ACT_DOUBLES] kp, kd, torque limit; nullptr: not set (srbm_wb_plant_set_actuators)
+    SrbmBody* d_fd_bodies = nullptr; // [batch][13]; nullptr: the controller's bodies (srbm_wb_plant_set_bodies_each)
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -417,6 +423,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_sum); (void)hipFree(h->d_sum_ref);
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
+    (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -586,6 +593,12 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
     // (... and the whole-body plant's (q, v); the tick log, like the step log, stays off)
     if (ok && src->d_wb) ok = wb_alloc(h) == 0 && cp(h->d_wb, src->d_wb, sizeof(double) * (19 + 18) * B);
+    // (... and the kind of the plant, its actuators, sub-steps and bodies)
+    h->fd_kind = src->fd_kind; h->fd_substeps = src->fd_substeps;
+    if (ok && src->d_fd_act)
+        ok = hipMalloc(&h->d_fd_act, sizeof(double) * WBFD_ACT_DOUBLES * B) == hipSuccess && cp(h->d_fd_act, src->d_fd_act, sizeof(double) * WBFD_ACT_DOUBLES * B);
+    if (ok && src->d_fd_bodies)
+        ok = hipMalloc(&h->d_fd_bodies, sizeof(SrbmBody) * 13 * B) == hipSuccess && cp(h->d_fd_bodies, src->d_fd_bodies, sizeof(SrbmBody) * 13 * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2181,11 +2194,135 @@ int srbm_wb_plant_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_de
     if (use_batch(h)) return -1;
     return launch_wb_plant(h, tick, tick_dt, q_dev, v_dev, qp_sol_dev, status_dev, nullptr, nullptr);
 }
+// ---- the torque-driven plant (srbm_wb_fd.hiph) ----
+static const char* const FD_NO_ACTUATORS = "the torque-driven plant has no actuators (srbm_wb_plant_set_actuators)";
+int srbm_wb_plant_set_kind(srbm_batch* h, int kind) {
+    if (!h) return fail("srbm_wb_plant_set_kind: bad arguments");
+    if (kind != 0 && kind != 1) return fail("srbm_wb_plant_set_kind: kind " + std::to_string(kind) + " (0: the QP-acceleration plant, 1: the torque-driven plant)");
+    h->fd_kind = kind;
+    return 0;
+}
+int srbm_wb_plant_set_actuators(srbm_batch* h, const double* kp, const double* kd, const double* torque_limit, int substeps) {
+    const std::string fn = "srbm_wb_plant_set_actuators";
+    if (!h || !kp || !kd || !torque_limit) return fail(fn + ": bad arguments");
+    if (substeps < 1) return fail(fn + ": substeps >= 1 is required");
+    const size_t B = h->batch;
+    for (size_t e = 0; e < 12 * B; e++) {
+        const std::string at = fn + ": instance " + std::to_string(e / 12) + ", joint " + std::to_string(e % 12) + ": ";
+        if (!std::isfinite(kp[e]) || kp[e] < 0.0) return fail(at + "kp must be finite and >= 0");
+        if (!std::isfinite(kd[e]) || kd[e] < 0.0) return fail(at + "kd must be finite and >= 0");
+        if (!(torque_limit[e] >= 0.0)) return fail(at + "the torque limit must be >= 0 (+inf: none)");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    Carve c;
+    const auto a = c.add<double>(WBFD_ACT_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    if (!h->d_fd_act) HIPCHK(hipMalloc(&h->d_fd_act, a.bytes()));
+    double* dst = c.host(a);
+    for (size_t b = 0; b < B; b++) {
+        std::memcpy(dst + WBFD_ACT_DOUBLES * b, kp + 12 * b, sizeof(double) * 12);
+        std::memcpy(dst + WBFD_ACT_DOUBLES * b + 12, kd + 12 * b, sizeof(double) * 12);
+        std::memcpy(dst + WBFD_ACT_DOUBLES * b + 24, torque_limit + 12 * b, sizeof(double) * 12);
+    }
+    HIPCHK(hipMemcpyAsync(h->d_fd_act, dst, a.bytes(), hipMemcpyHostToDevice, h->stream));
+    h->fd_substeps = substeps;
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_set_bodies_each(srbm_batch* h, const double* body_mass, const double* body_com, const double* body_inertia) {
+    const std::string fn = "srbm_wb_plant_set_bodies_each";
+    if (!h || !body_mass || !body_com || !body_inertia) return fail(fn + ": bad arguments");
+    const size_t B = h->batch;
+    for (size_t e = 0; e < 13 * B; e++) {
+        const std::string at = fn + ": instance " + std::to_string(e / 13) + ", body " + std::to_string(e % 13) + ": ";
+        if (!std::isfinite(body_mass[e]) || body_mass[e] <= 0.0) return fail(at + "the mass must be finite and > 0");
+        for (int i = 0; i < 3; i++) if (!std::isfinite(body_com[3 * e + i])) return fail(at + "the centre of mass is not finite");
+        for (int i = 0; i < 9; i++) if (!std::isfinite(body_inertia[9 * e + i])) return fail(at + "the inertia is not finite");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    Carve c;
+    const auto a = c.add<SrbmBody>(13 * B);
+    if (c.stage(h)) return -1;
+    if (!h->d_fd_bodies) HIPCHK(hipMalloc(&h->d_fd_bodies, a.bytes()));
+    SrbmBody* dst = c.host(a);
+    for (size_t e = 0; e < 13 * B; e++) {
+        dst[e].mass = body_mass[e];
+        std::memcpy(dst[e].com, body_com + 3 * e, sizeof(double) * 3);
+        std::memcpy(dst[e].I, body_inertia + 9 * e, sizeof(double) * 9);
+    }
+    HIPCHK(hipMemcpyAsync(h->d_fd_bodies, dst, a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+// the plant's bodies and their stride per instance: its own, or the controller's for every instance
+static const SrbmBody* fd_bodies(const srbm_batch* h, int* stride) {
+    *stride = h->d_fd_bodies ? 13 : 0;
+    return h->d_fd_bodies ? h->d_fd_bodies : reinterpret_cast<const SrbmBody*>(h->d_wbc);
+}
+static int fd_usable(srbm_batch* h, const char* fn) {
+    if (need_legs(h)) return -1;
+    if (!h->d_wbc && !h->d_fd_bodies)
+        return fail(std::string(fn) + ": the whole-body model has not been set (srbm_set_wbc_model), and the plant has no bodies of its own (srbm_wb_plant_set_bodies_each)");
+    return 0;
+}
+int srbm_wb_forward_dynamics_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* tau_dev, const int* contact_dev, double* sol_dev, int* status_dev) {
+    if (!h || !q_dev || !v_dev || !tau_dev || !contact_dev || !sol_dev || !status_dev) return fail("srbm_wb_forward_dynamics: bad arguments");
+    if (fd_usable(h, "srbm_wb_forward_dynamics") || use_batch(h)) return -1;
+    int stride = 0;
+    const SrbmBody* bodies = fd_bodies(h, &stride);
+    hipLaunchKernelGGL(srbm_k_wb_forward_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, q_dev, v_dev, tau_dev, contact_dev, sol_dev, status_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_forward_dynamics(srbm_batch* h, const double* q, const double* v, const double* tau, const int* contact, double* sol, int* status) {
+    if (!h || !q || !v || !tau || !contact || !sol) return fail("srbm_wb_forward_dynamics: bad arguments");
+    if (fd_usable(h, "srbm_wb_forward_dynamics")) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = h->batch;
+    Carve c;                                          // in: q, v, tau, contact; out: sol, status
+    const auto iq = c.add<double>(19 * B), iv = c.add<double>(18 * B), it = c.add<double>(12 * B);
+    const auto icon = c.add<int>(4 * B);
+    const auto os = c.add<double>(WBC_NMAX * B);
+    const auto ost = c.add<int>(B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(iq), q, iq.bytes());
+    memcpy(c.host(iv), v, iv.bytes());
+    memcpy(c.host(it), tau, it.bytes());
+    memcpy(c.host(icon), contact, icon.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(iq), c.host(iq), Carve::span(iq, icon), hipMemcpyHostToDevice, h->stream));
+    if (srbm_wb_forward_dynamics_dev(h, c.dev(iq), c.dev(iv), c.dev(it), c.dev(icon), c.dev(os), c.dev(ost))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(os), c.dev(os), Carve::span(os, ost), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(sol, c.host(os), os.bytes());
+    if (status) memcpy(status, c.host(ost), ost.bytes());
+    return 0;
+}
+// the torque-driven plant step of tick `tick` on the batch's stream; qp_sol: the tick's, for the record (lg != nullptr)
+static int launch_wb_fd(srbm_batch* h, int tick, double tick_dt, double* q, double* v, const double* control, const int* contact, const int* status,
+                        const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
+    const double* push = h->push_set ? h->d_push : nullptr;
+    int stride = 0;
+    const SrbmBody* bodies = fd_bodies(h, &stride);
+    const SrbmFdArgs fa{bodies, stride, h->d_fd_act, h->fd_substeps, control, contact, qp_sol, sol_out};
+    if (lg) hipLaunchKernelGGL((srbm_k_wb_fd_step<true>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, *lg);
+    else hipLaunchKernelGGL((srbm_k_wb_fd_step<false>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next,
+                            SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0});
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* control_dev, const int* contact_dev,
+                        const int* status_dev, double* sol_dev) {
+    if (!h || !q_dev || !v_dev || !control_dev || !contact_dev || !status_dev) return fail("srbm_wb_fd_step_dev: bad arguments");
+    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_fd_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
+    if (fd_usable(h, "srbm_wb_fd_step_dev")) return -1;
+    if (!h->d_fd_act) return fail(std::string("srbm_wb_fd_step_dev: ") + FD_NO_ACTUATORS);
+    if (use_batch(h)) return -1;
+    return launch_wb_fd(h, tick, tick_dt, q_dev, v_dev, control_dev, contact_dev, status_dev, nullptr, sol_dev, nullptr, nullptr);
+}
 int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt) {
     const std::string fn = "srbm_controller_advance";
     if (!h) return fail(fn + ": bad arguments (NULL handle)");
     if (!h->d_wb) return fail(fn + ": the whole-body plant state has not been set (srbm_wb_plant_set_state)");
     if (tick_usable(h)) return -1;
+    if (h->fd_kind == 1 && !h->d_fd_act) return fail(fn + ": " + FD_NO_ACTUATORS);
     if (first_tick < 0 || ticks < 0 || ticks > INT_MAX - first_tick) return fail(fn + ": first_tick >= 0 and ticks >= 0 are required");
     if (ticks_per_update < 1) return fail(fn + ": ticks_per_update >= 1 is required");
     if (!std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(fn + ": a finite tick_dt > 0 is required");
@@ -2212,7 +2349,9 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
         const bool update = k > 0 && k % ticks_per_update == 0;
         if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
-        if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
+        if (h->fd_kind == 1) {
+            if (launch_wb_fd(h, k, tick_dt, w.q, w.v, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
+        } else if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
         if (h->d_tlog) h->tlog_used++;
         // the hand-off of mpc_controller.cpp:142-156: the state and foot positions of THIS tick to the solve, the new trajectories in force from tick k + 1
         if (update && srbm_get_real_time_update_dev(h, w.state, time, w.ee)) return -1;

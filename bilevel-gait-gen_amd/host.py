@@ -232,6 +232,12 @@ int srbm_tick_log_reset(srbm_batch*)
 int srbm_tick_log_count(srbm_batch*, int*)
 int srbm_tick_log_get(srbm_batch*, int, int, double*)
 int srbm_tick_log_copy_dev(srbm_batch*, int, int, dev*)
+int srbm_wb_plant_set_kind(srbm_batch*, int)
+int srbm_wb_plant_set_actuators(srbm_batch*, double*, double*, double*, int)
+int srbm_wb_plant_set_bodies_each(srbm_batch*, double*, double*, double*)
+int srbm_wb_forward_dynamics(srbm_batch*, double*, double*, double*, int*, double*, int*)
+int srbm_wb_forward_dynamics_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_wb_fd_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

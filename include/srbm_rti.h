@@ -559,7 +559,8 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *     0, 1      tick index k, time t_k
  *     2         targets status
  *     3, 4      QP status, QP iterations
- *     5         flags: bit 0 the push was applied in this tick, bit 1 an MPC update followed this tick, bit 2 the plant coasted
+ *     5         flags: bit 0 the push was applied in this tick, bit 1 an MPC update followed this tick, bit 2 the plant coasted (plant kind 0
+ *               only: the torque-driven plant never coasts on a zero control action), bit 3 a factorisation of the torque-driven plant broke down
  *     6..12     base position and quaternion of the measured q
  *     13..18    base twist of the measured v
  *     19..30    torques (control[24..36))
@@ -567,7 +568,15 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *     43..46    desired contacts [4]
  *     47..50    foot heights (ee[.][2]) [4]
  *     51..56    base acceleration a[0..6)
- *     57..63    0
+ *     57..63    plant kind 0: 0.  Plant kind 1 (the torque-driven plant, below), 58..62 from the LAST sub-step of the tick:
+ *       57      the plant kind (1)
+ *       58      number of joints whose torque was clamped
+ *       59      max_j |tau_j - tau_ff,j|: what the PD loop and the limits changed
+ *       60      the smallest vertical plant force over the stance feet, 0 with none; negative: the held foot pulls (the plant's stated limit)
+ *       61      |a_plant - a_QP|_inf over the 18 accelerations
+ *       62      |F_plant - F_QP|_inf over the stance feet
+ *       63      0
+ *     Fields 31..42 and 51..56 are the QP's forces and acceleration for either kind.
  * The entries have the semantics of their srbm_step_log_* counterparts: srbm_tick_log_enable allocates max_ticks x batch records and sets the cursor to
  * 0 (0 disables and frees); capacity is checked before anything is launched; get (host, synchronous) and copy_dev (on the stream) fail for a slot
  * range outside [0, ticks_logged) and when no log is enabled.  A clone has logging off. */
@@ -578,6 +587,52 @@ int srbm_tick_log_reset(srbm_batch* h);                          /* cursor 0, bu
 int srbm_tick_log_count(srbm_batch* h, int* ticks_logged);
 int srbm_tick_log_get(srbm_batch* h, int first_slot, int count, double* out);
 int srbm_tick_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev);
+
+/* ---- the torque-driven whole-body plant ----
+ * The plant above integrates the QP's own accelerations: the torques and joint targets of the control action act on nothing, and the robot is exactly
+ * the controller's model.  The torque-driven plant (kind 1) takes the control action and computes its own accelerations, per sub-step of h / S
+ * (S = substeps, h / S one rounded quotient) on the plant's current (q, v):
+ *     tau_j = clamp(tau_ff,j + kp_j (q_des,j - q_j) + kd_j (v_des,j - v_j), +-torque_limit_j)     tau_ff = control[24..36), q_des = control[0..12),
+ *             v_des = control[12..24) of the tick, held over its sub-steps; the PD terms on the current (q, v), as position and velocity actuators
+ *             (the reference's robot: controllers/include/controller.h:62-73, the actuators before the motors)
+ *     M a - Js' F = S' tau - C v - g,  Js a = -Jsdot v      the constrained forward dynamics of the floating-base model on the PLANT'S OWN bodies with
+ *             the planned stance feet held: 18 + 3 nc unknowns, nc the feet in contact, F stacked in foot order as qp_sol has it; solved exactly
+ *             (LDL' of the quasi-definite matrix, no regularisation)
+ *     v <- v + (h / S) a,  q <- pinocchio::integrate(q, v, h / S)
+ * The push rule is the tick's (t_k < push_time <= t_k + h), applied to the velocity after the LAST sub-step's velocity update and before its
+ * configuration step (S = 1: the order of the other plant); the impulse keeps using the instance's mass and Ir^-1.
+ * What it is NOT: no ground and no collision -- a held foot pulls when the dynamics ask for it (tick log field 60) --, no contact solver, no
+ * AdjustForCurrentContacts.  Where it differs from kind 0: to an instance whose tick returned a zero control action the actuators are OFF (tau = 0,
+ * no PD) and the plant still runs, so the robot goes limp; the kind-0 plant coasts.  A sub-step whose factorisation meets a pivot that is not finite
+ * or has the wrong sign takes a = 0 (flags bit 3 of the tick): no NaN reaches (q, v).
+ *
+ * srbm_wb_plant_set_kind: the plant srbm_controller_advance launches; 0 the QP-acceleration plant (the default), 1 the torque-driven plant.
+ * Refused: a kind outside {0, 1}. */
+int srbm_wb_plant_set_kind(srbm_batch* h, int kind);
+/* The actuators of the torque-driven plant, per instance: kp[batch][12], kd[batch][12], torque_limit[batch][12] (+inf: none), and the batch-wide
+ * number of sub-steps per tick.  These are the ROBOT'S actuator gains (the reference keeps them in its MuJoCo XML), not the QP's acceleration-level
+ * kp_joint_gains / kd_joint_gains.  Refused, naming the instance and joint: kp or kd negative or not finite; a limit that is NaN or < 0;
+ * substeps < 1. */
+int srbm_wb_plant_set_actuators(srbm_batch* h, const double* kp, const double* kd, const double* torque_limit, int substeps);
+/* The plant's own bodies per instance, in the layout of srbm_wbc_model: body_mass[batch][13], body_com[batch][13][3], body_inertia[batch][13][9].
+ * Never called: the plant uses the controller's bodies (srbm_set_wbc_model).  One batch can so sweep a payload or inertia error.  Refused, naming the
+ * instance and body: a mass <= 0, an entry that is not finite. */
+int srbm_wb_plant_set_bodies_each(srbm_batch* h, const double* body_mass, const double* body_com, const double* body_inertia);
+/* The solve alone on the plant's bodies: q[batch][19], v[batch][18], tau[batch][12], contact[batch][4] -> sol[batch][30] = a[18] then F stacked in
+ * foot order (0 past 18 + 3 nc), status[batch] (may be NULL) 0, or 1 for a factorisation breakdown (sol is then 0).  Refused without leg kinematics
+ * and without bodies (neither a whole-body model nor the plant's own). */
+int srbm_wb_forward_dynamics(srbm_batch* h, const double* q, const double* v, const double* tau, const int* contact, double* sol, int* status);
+/* ... on device pointers: one launch on the batch's stream, no copy, no synchronisation */
+int srbm_wb_forward_dynamics_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* tau_dev, const int* contact_dev, double* sol_dev,
+                                 int* status_dev);
+/* The torque-driven plant step of tick `tick` on the caller's device arrays, the counterpart of srbm_wb_plant_step_dev: q_dev[batch][19],
+ * v_dev[batch][18] in place from control_dev[batch][36], contact_dev[batch][4], status_dev[batch][2] as srbm_control_tick_dev returned them;
+ * sol_dev (may be NULL) [batch][30] <- (a, F) of the last sub-step.  One launch on the batch's stream, no copy, no synchronisation; never logs (a
+ * host can drive the loop itself and be compared bit for bit).  Refused without actuators, leg kinematics or bodies.
+ * srbm_controller_advance launches this kernel instead of the QP-acceleration plant's when the kind is 1 (refused then without actuators); nothing
+ * else in it changes.  srbm_batch_clone carries the kind, the actuators, the sub-steps and the bodies. */
+int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* control_dev, const int* contact_dev,
+                        const int* status_dev, double* sol_dev);
 
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */

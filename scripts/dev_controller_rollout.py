@@ -4,6 +4,9 @@ medians and spreads.
   (a) entry      srbm_controller_advance, all ticks in one call (without and with a tick log: the difference is what the logged kernel adds)
   (b) chain      the loop driven from the host: srbm_control_tick_dev, srbm_wb_plant_step_dev, srbm_get_real_time_update_dev
   (c) plant      the plant-step kernel alone (srbm_wb_plant_step_dev, unlogged), 200 launches on the outputs of one tick
+  (d) torque     srbm_controller_advance with the torque-driven plant (srbm_wb_plant_set_kind 1: PD 20 / 0.5, the configured torque bounds as
+                 limits, the controller's bodies), logged, S = 1 and S = 4 sub-steps per tick; beside (a) this is what the plant kind costs.  And
+                 its step kernel alone (srbm_wb_fd_step_dev, S = 1 and 4), as (c)
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -18,9 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from srbm_loader import host
 from srbm_loader.control_tick import ControlTick
-from srbm_loader.controller_rollout import ControllerRollout, TICK_LOG_FIELDS as F, FLAG_COAST
+from srbm_loader.controller_rollout import ControllerRollout, TICK_LOG_FIELDS, TORQUE_PLANT_LOG_FIELDS, FLAG_COAST, FLAG_BREAKDOWN, PLANT_TORQUE_DRIVEN
 from srbm_loader.workloads import config_b_instance, instances
 
+F = dict(TICK_LOG_FIELDS, **TORQUE_PLANT_LOG_FIELDS)
 B, TICKS, TPU, DT, LIMIT_S = 256, 200, 50, 1e-3, 60.0
 RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 
@@ -34,7 +38,8 @@ def main():
     base = host.BatchMPC.cold_start(cfg, states, ees)
     q_init = np.tile(np.array(cfg['init_config'], float), (B, 1))
     q0, v0, _, st = base.clone().get_targets_from_traj(0.0, q_init)          # the plant starts on the targets of tick 0
-    res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': []}
+    res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': [], 'torque_s1_logged': [], 'torque_s4_logged': [], 'fd_step_s1': [], 'fd_step_s4': []}
+    kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
     f64 = dict(dtype=torch.float64, device='cuda')
 
@@ -66,6 +71,22 @@ def main():
                 info['targets_not_ok'] = int((log[:, :, F['targets_status']] != 0).sum())
                 info['base_height_range'] = [float(log[:, :, 8].min()), float(log[:, :, 8].max())]
             info['finite_' + name] = bool(np.all(np.isfinite(R.state()[0])))
+        # (d) the torque-driven plant
+        for S in (1, 4):
+            name = 'torque_s%d_logged' % S
+            g, R = fresh(TICKS + 3)
+            R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, S)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log = R.tick_log()
+            info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
+                              zero_action_ticks=int((log[:, :, F['qp_status']] > 1).sum()),
+                              breakdown_ticks=int(((log[:, :, F['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
+                              clamped_ticks=int((log[:, :, F['clamped_joints']] > 0).sum()), min_stance_fz=float(log[:, :, F['min_stance_fz']].min()),
+                              pulling_ticks=int((log[:, :, F['min_stance_fz']] < 0).sum()),
+                              median_accel_mismatch=float(np.median(log[:, :, F['accel_mismatch']])), max_accel_mismatch=float(log[:, :, F['accel_mismatch']].max()))
         # (b) the same loop from the host, on torch's buffers, on the batch's stream
         g, R = fresh()
         T = ControlTick(g)
@@ -95,6 +116,19 @@ def main():
             plant()
             signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
             res['plant'].append(timed(g, plant))
+
+            # ... and the torque-driven step kernel alone, on the same outputs
+            for S in (1, 4):
+                R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, S)
+                q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64))
+
+                def fd_step():
+                    for k in range(TICKS):
+                        R.fd_step_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), ctl_d.data_ptr(), con_d.data_ptr(), st_d.data_ptr())
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                fd_step()
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                res['fd_step_s%d' % S].append(timed(g, fd_step))
     signal.setitimer(signal.ITIMER_REAL, 0)
     med = {k: float(np.median(v)) for k, v in res.items()}
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,

@@ -3,7 +3,7 @@
 # source: srbm_capi.hip, which includes the kernels of csrc/*.hiph -- the IPM's are srbm_k3_lds / _rows / _normal / _ipm.hiph, the gait step's srbm_gait_candidates / _sens / _grad / _lp.hiph, the linearised model srbm_lin.hiph): VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, static LDS and a short
 # hash of its disassembly; per out-of-line device function the hash alone.  Lines sorted by name.  The hash drops the `//` comments (addresses,
 # encodings) and masks the literal of every s_add_u32 / s_addc_u32 within three instructions after an s_getpc_b64: those are PC-relative
-# offsets, which change whenever any function moves in the code object; trailing s_nop padding is dropped too.  Two builds whose outputs
+# offsets, which change whenever any function moves in the code object; the padding after a function (s_nop, zero bytes) is dropped too.  Two builds whose outputs
 # agree have the same instructions: `diff` the listing of the parent's build with the branch's, for each library (scripts/README.md).
 LIB=$1
 T=$(mktemp -d)
@@ -32,8 +32,8 @@ def isa_hashes(co):
         elif since_getpc <= 3 and re.match(r's_addc?_u32 ', ins):
             ins = re.sub(r',\s*(0x[0-9a-fA-F]+|-?\d+)$', ', LIT', ins)
         funcs[name].append(ins)
-    for v in funcs.values():                      # the s_nop padding after the last function of the code object
-        while v and v[-1].startswith('s_nop'):
+    for v in funcs.values():                      # the padding after a function: s_nop, or zero bytes (objdump prints them as `...`)
+        while v and (v[-1].startswith('s_nop') or v[-1] == '...'):
             v.pop()
     return {n: hashlib.sha1('\n'.join(v).encode()).hexdigest()[:12] for n, v in funcs.items()}
 
