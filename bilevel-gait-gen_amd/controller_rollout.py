@@ -11,6 +11,7 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.set_state(q, v)                     the plant's (q, v)
     mpc.plant_set_push(time, impulse)     optional: one push per instance
     R.set_plant(1, kp, kd, limit, 4)      optional: the torque-driven plant, 4 sub-steps per tick; R.set_plant_bodies(...): its own bodies
+    R.set_ground(ground)                  optional, with set_plant(1, ...): a compliant ground [batch][8] under the torque-driven plant's feet
     R.tick_log_enable(200)                optional: one record per tick and instance
     R.advance(0, 200, 50, 1e-3)           200 ticks of 1 ms, an MPC update every 50; asynchronous
     q, v = R.state(); log = R.tick_log()"""
@@ -27,12 +28,27 @@ TICK_LOG_FIELDS = dict(tick=0, time=1, targets_status=2, qp_status=3, qp_iters=4
                        torques=slice(19, 31), contact_forces=slice(31, 43), contact=slice(43, 47), foot_heights=slice(47, 51), base_accel=slice(51, 57))
 # ... and what the torque-driven plant writes into [57, 63) (field 63 stays 0): 58..62 are of the last sub-step of the tick
 TORQUE_PLANT_LOG_FIELDS = dict(plant_kind=57, clamped_joints=58, torque_deviation=59, min_stance_fz=60, accel_mismatch=61, force_mismatch=62)
+# ... and what it writes with a ground set (set_ground): 57..59 as above, 60..63 of the ground; 58..63 are of the last sub-step of the tick
+GROUND_PLANT_LOG_FIELDS = dict(plant_kind=57, clamped_joints=58, torque_deviation=59, min_planned_stance_fz=60, accel_mismatch=61, force_mismatch=62,
+                               ground_word=63)
+GROUND_WORD_OFFSET = 4096
+GROUND_DOUBLES, CONTACT_STATE_DOUBLES = 8, 12
 FLAG_PUSH, FLAG_UPDATE, FLAG_COAST, FLAG_BREAKDOWN = 1, 2, 4, 8
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
 
 
 def _d(a):
     return a.ctypes.data_as(_dp)
+
+
+def decode_ground_word(field63):
+    """field 63 of a record (a number or an array of them) -> dict(ground=bool, in_contact, slipping, plan_differs), the last three with a trailing
+    axis over the four feet.  ground is False (and the rest all False) for a record written without a ground, whose field 63 is 0"""
+    w = np.asarray(field63).astype(np.int64)
+    ground = w >= GROUND_WORD_OFFSET
+    word = np.where(ground, w - GROUND_WORD_OFFSET, 0)
+    bits = lambda first: ((word[..., None] >> (first + np.arange(4))) & 1).astype(bool)
+    return dict(ground=ground, in_contact=bits(0), slipping=bits(4), plan_differs=bits(8))
 
 
 class ControllerRollout:
@@ -100,6 +116,43 @@ class ControllerRollout:
         """the torque-driven plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from control[batch][36],
         contact[batch][4], status[batch][2] of control_tick_dev; sol: None or [batch][30] <- (a, F) of the last sub-step; asynchronous, never logs"""
         self.mpc._chk(self.L.srbm_wb_fd_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, control, contact, status, sol))
+
+    # ---- the ground of the torque-driven plant ----
+    def set_ground(self, ground):
+        """a compliant ground under the torque-driven plant: one [8] or [batch][8] = z0 (-inf: none for the instance), k_n, d_n, mu, k_t, d_t, 0, 0;
+        None removes it (kind 1 then holds the planned feet again)"""
+        m = self.mpc
+        m._chk(self.L.srbm_wb_plant_set_ground(m.h, None if ground is None else _d(m._bcast(ground, GROUND_DOUBLES))))
+
+    def contact_state(self):
+        """-> cs[batch][4][3]: per foot in_contact (0 | 1), anchor_x, anchor_y, after the work queued so far"""
+        m = self.mpc
+        cs = np.zeros((m.batch, 4, 3))
+        m._chk(self.L.srbm_wb_plant_get_contact_state(m.h, _d(cs)))
+        return cs
+
+    def set_contact_state(self, cs):
+        """one [4][3] or [batch][4][3] (set_state resets it to no foot in contact)"""
+        m = self.mpc
+        m._chk(self.L.srbm_wb_plant_set_contact_state(m.h, _d(m._bcast(cs, CONTACT_STATE_DOUBLES))))
+
+    def ground_dynamics(self, q, v, tau, cs):
+        """the contact law and the 18-row solve alone on the plant's bodies -> sol[batch][30] (a, then F[4][3] in foot order), cs_out[batch][4][3],
+        status[batch]"""
+        m = self.mpc
+        sol, out, st = np.zeros((m.batch, 30)), np.zeros((m.batch, 4, 3)), np.zeros(m.batch, np.int32)
+        m._chk(self.L.srbm_wb_ground_dynamics(m.h, _d(m._bcast(q, 19)), _d(m._bcast(v, 18)), _d(m._bcast(tau, 12)), _d(m._bcast(cs, CONTACT_STATE_DOUBLES)),
+                                              _d(sol), _d(out), st.ctypes.data_as(_ip)))
+        return sol, out, st
+
+    def ground_dynamics_dev(self, q, v, tau, cs_in, sol, cs_out, status):
+        """the same on device pointers (ints); asynchronous"""
+        self.mpc._chk(self.L.srbm_wb_ground_dynamics_dev(self.mpc.h, q, v, tau, cs_in, sol, cs_out, status))
+
+    def ground_step_dev(self, tick, tick_dt, q, v, cs, control, status, sol=None):
+        """the ground step alone on device pointers (ints): q[batch][19], v[batch][18], cs[batch][12] in place from control[batch][36] and
+        status[batch][2] of control_tick_dev; sol: None or [batch][30] <- (a, F) of the last sub-step; asynchronous, never logs"""
+        self.mpc._chk(self.L.srbm_wb_ground_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, cs, control, status, sol))
 
     # ---- the tick log ----
     def tick_log_enable(self, max_ticks):

@@ -22,6 +22,7 @@
 #include "srbm_tick.hiph"
 #include "srbm_wb_plant.hiph"
 #include "srbm_wb_fd.hiph"
+#include "srbm_wb_ground.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
@@ -109,6 +110,9 @@ struct srbm_batch {
     int fd_substeps = 1;
     double* d_fd_act = nullptr;      // [batch][WBFD_ACT_DOUBLES] kp, kd, torque limit; nullptr: not set (srbm_wb_plant_set_actuators)
     SrbmBody* d_fd_bodies = nullptr; // [batch][13]; nullptr: the controller's bodies (srbm_wb_plant_set_bodies_each)
+    // the ground of the torque-driven plant (srbm_wb_ground.hiph)
+    double* d_ground = nullptr;      // [batch][WBG_GROUND_DOUBLES]; nullptr: no ground, kind 1 holds the planned feet (srbm_wb_plant_set_ground)
+    double* d_cs = nullptr;          // the contact state [batch][WBG_CS_DOUBLES], allocated with d_wb
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -424,6 +428,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
+    (void)hipFree(h->d_ground); (void)hipFree(h->d_cs);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -452,6 +457,7 @@ static int wb_alloc(srbm_batch* h) {
     const size_t B = h->batch;
     if (!h->d_wb) HIPCHK(hipMalloc(&h->d_wb, sizeof(double) * WB_DOUBLES * B));
     if (!h->d_wb_int) HIPCHK(hipMalloc(&h->d_wb_int, sizeof(int) * WB_INTS * B));
+    if (!h->d_cs) HIPCHK(hipMalloc(&h->d_cs, sizeof(double) * WBG_CS_DOUBLES * B));
     return 0;
 }
 static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
@@ -592,13 +598,16 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     // (the control tick's q_des_ goes along)
     if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
     // (... and the whole-body plant's (q, v); the tick log, like the step log, stays off)
-    if (ok && src->d_wb) ok = wb_alloc(h) == 0 && cp(h->d_wb, src->d_wb, sizeof(double) * (19 + 18) * B);
+    if (ok && src->d_wb) ok = wb_alloc(h) == 0 && cp(h->d_wb, src->d_wb, sizeof(double) * (19 + 18) * B) && cp(h->d_cs, src->d_cs, sizeof(double) * WBG_CS_DOUBLES * B);
     // (... and the kind of the plant, its actuators, sub-steps and bodies)
     h->fd_kind = src->fd_kind; h->fd_substeps = src->fd_substeps;
     if (ok && src->d_fd_act)
         ok = hipMalloc(&h->d_fd_act, sizeof(double) * WBFD_ACT_DOUBLES * B) == hipSuccess && cp(h->d_fd_act, src->d_fd_act, sizeof(double) * WBFD_ACT_DOUBLES * B);
     if (ok && src->d_fd_bodies)
         ok = hipMalloc(&h->d_fd_bodies, sizeof(SrbmBody) * 13 * B) == hipSuccess && cp(h->d_fd_bodies, src->d_fd_bodies, sizeof(SrbmBody) * 13 * B);
+    // (... and its ground; the contact state went with (q, v))
+    if (ok && src->d_ground)
+        ok = hipMalloc(&h->d_ground, sizeof(double) * WBG_GROUND_DOUBLES * B) == hipSuccess && cp(h->d_ground, src->d_ground, sizeof(double) * WBG_GROUND_DOUBLES * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2170,6 +2179,7 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     const WbBuf w = wb_buf(h);
     HIPCHK(hipMemcpyAsync(w.q, q, sizeof(double) * 19 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(w.v, v, sizeof(double) * 18 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_cs, 0, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch, h->stream));          // no foot in contact
     return srbm_synchronize(h);
 }
 int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
@@ -2317,6 +2327,123 @@ int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, 
     if (use_batch(h)) return -1;
     return launch_wb_fd(h, tick, tick_dt, q_dev, v_dev, control_dev, contact_dev, status_dev, nullptr, sol_dev, nullptr, nullptr);
 }
+// ---- the ground of the torque-driven plant (srbm_wb_ground.hiph) ----
+static const char* const WB_NO_STATE = "the whole-body plant state has not been set (srbm_wb_plant_set_state)";
+int srbm_wb_plant_set_ground(srbm_batch* h, const double* ground) {
+    const std::string fn = "srbm_wb_plant_set_ground";
+    if (!h) return fail(fn + ": bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (!ground) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->d_ground) HIPCHK(hipFree(h->d_ground));
+        h->d_ground = nullptr;
+        return 0;
+    }
+    const size_t B = h->batch;
+    static const char* const names[WBG_GROUND_DOUBLES] = {"the ground height", "the normal stiffness", "the normal damping", "the friction coefficient",
+                                                          "the tangential stiffness", "the tangential damping", "reserved", "reserved"};
+    for (size_t e = 0; e < WBG_GROUND_DOUBLES * B; e++) {
+        const int f = (int)(e % WBG_GROUND_DOUBLES);
+        const double x = ground[e];
+        const std::string at = fn + ": instance " + std::to_string(e / WBG_GROUND_DOUBLES) + ", field " + std::to_string(f) + " (" + names[f] + "): ";
+        if (f == 0) { if (!(std::isfinite(x) || (std::isinf(x) && x < 0.0))) return fail(at + "must be finite, or -inf for no ground"); }
+        else if (f == 1 || f == 4) { if (!std::isfinite(x) || x <= 0.0) return fail(at + "must be finite and > 0"); }
+        else if (f < 6) { if (!std::isfinite(x) || x < 0.0) return fail(at + "must be finite and >= 0"); }
+        else if (x != 0.0 || std::signbit(x)) return fail(at + "must be 0");
+    }
+    Carve c;
+    const auto a = c.add<double>(WBG_GROUND_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    if (!h->d_ground) HIPCHK(hipMalloc(&h->d_ground, a.bytes()));
+    std::memcpy(c.host(a), ground, a.bytes());
+    HIPCHK(hipMemcpyAsync(h->d_ground, c.host(a), a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_get_contact_state(srbm_batch* h, double* cs) {
+    if (!h || !cs) return fail("srbm_wb_plant_get_contact_state: bad arguments");
+    if (!h->d_wb) return fail(WB_NO_STATE);
+    return fetch(h, {{cs, h->d_cs, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch}});
+}
+int srbm_wb_plant_set_contact_state(srbm_batch* h, const double* cs) {
+    const std::string fn = "srbm_wb_plant_set_contact_state";
+    if (!h || !cs) return fail(fn + ": bad arguments");
+    if (!h->d_wb) return fail(WB_NO_STATE);
+    const size_t B = h->batch;
+    for (size_t e = 0; e < WBG_CS_DOUBLES * B; e++) {
+        const std::string at = fn + ": instance " + std::to_string(e / WBG_CS_DOUBLES) + ", foot " + std::to_string(e % WBG_CS_DOUBLES / 3) + ": ";
+        if (e % 3 == 0) { if (cs[e] != 0.0 && cs[e] != 1.0) return fail(at + "in_contact must be 0 or 1"); }
+        else if (!std::isfinite(cs[e])) return fail(at + "the anchor is not finite");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    Carve c;
+    const auto a = c.add<double>(WBG_CS_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    std::memcpy(c.host(a), cs, a.bytes());
+    HIPCHK(hipMemcpyAsync(h->d_cs, c.host(a), a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+static int ground_usable(srbm_batch* h, const char* fn) {
+    if (fd_usable(h, fn)) return -1;
+    if (!h->d_ground) return fail(std::string(fn) + ": the torque-driven plant has no ground (srbm_wb_plant_set_ground)");
+    return 0;
+}
+int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* tau_dev, const double* cs_in_dev, double* sol_dev,
+                                double* cs_out_dev, int* status_dev) {
+    if (!h || !q_dev || !v_dev || !tau_dev || !cs_in_dev || !sol_dev || !cs_out_dev || !status_dev) return fail("srbm_wb_ground_dynamics: bad arguments");
+    if (ground_usable(h, "srbm_wb_ground_dynamics") || use_batch(h)) return -1;
+    int stride = 0;
+    const SrbmBody* bodies = fd_bodies(h, &stride);
+    hipLaunchKernelGGL(srbm_k_wb_ground_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_ground, q_dev, v_dev, tau_dev, cs_in_dev,
+                       sol_dev, cs_out_dev, status_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_ground_dynamics(srbm_batch* h, const double* q, const double* v, const double* tau, const double* cs_in, double* sol, double* cs_out, int* status) {
+    if (!h || !q || !v || !tau || !cs_in || !sol || !cs_out) return fail("srbm_wb_ground_dynamics: bad arguments");
+    if (ground_usable(h, "srbm_wb_ground_dynamics")) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = h->batch;
+    Carve c;                                          // in: q, v, tau, cs; out: sol, cs, status
+    const auto iq = c.add<double>(19 * B), iv = c.add<double>(18 * B), it = c.add<double>(12 * B), ic = c.add<double>(WBG_CS_DOUBLES * B);
+    const auto os = c.add<double>(WBC_NMAX * B), oc = c.add<double>(WBG_CS_DOUBLES * B);
+    const auto ost = c.add<int>(B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(iq), q, iq.bytes());
+    memcpy(c.host(iv), v, iv.bytes());
+    memcpy(c.host(it), tau, it.bytes());
+    memcpy(c.host(ic), cs_in, ic.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(iq), c.host(iq), Carve::span(iq, ic), hipMemcpyHostToDevice, h->stream));
+    if (srbm_wb_ground_dynamics_dev(h, c.dev(iq), c.dev(iv), c.dev(it), c.dev(ic), c.dev(os), c.dev(oc), c.dev(ost))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(os), c.dev(os), Carve::span(os, ost), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(sol, c.host(os), os.bytes());
+    memcpy(cs_out, c.host(oc), oc.bytes());
+    if (status) memcpy(status, c.host(ost), ost.bytes());
+    return 0;
+}
+// the ground step of tick `tick` on the batch's stream; contact (the plan's) and qp_sol: the tick's, for the record (lg != nullptr)
+static int launch_wb_ground(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
+                            const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
+    const double* push = h->push_set ? h->d_push : nullptr;
+    int stride = 0;
+    const SrbmBody* bodies = fd_bodies(h, &stride);
+    const SrbmFdArgs fa{bodies, stride, h->d_fd_act, h->fd_substeps, control, contact, qp_sol, sol_out};
+    const SrbmGroundArgs ga{h->d_ground, cs};
+    if (lg) hipLaunchKernelGGL((srbm_k_wb_ground_step<true>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, *lg);
+    else hipLaunchKernelGGL((srbm_k_wb_ground_step<false>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next,
+                            SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0});
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, double* cs_dev, const double* control_dev, const int* status_dev,
+                            double* sol_dev) {
+    if (!h || !q_dev || !v_dev || !cs_dev || !control_dev || !status_dev) return fail("srbm_wb_ground_step_dev: bad arguments");
+    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_ground_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
+    if (ground_usable(h, "srbm_wb_ground_step_dev")) return -1;
+    if (!h->d_fd_act) return fail(std::string("srbm_wb_ground_step_dev: ") + FD_NO_ACTUATORS);
+    if (use_batch(h)) return -1;
+    return launch_wb_ground(h, tick, tick_dt, q_dev, v_dev, cs_dev, control_dev, nullptr, status_dev, nullptr, sol_dev, nullptr, nullptr);
+}
 int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt) {
     const std::string fn = "srbm_controller_advance";
     if (!h) return fail(fn + ": bad arguments (NULL handle)");
@@ -2349,7 +2476,9 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
         const bool update = k > 0 && k % ticks_per_update == 0;
         if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
-        if (h->fd_kind == 1) {
+        if (h->fd_kind == 1 && h->d_ground) {
+            if (launch_wb_ground(h, k, tick_dt, w.q, w.v, h->d_cs, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
+        } else if (h->fd_kind == 1) {
             if (launch_wb_fd(h, k, tick_dt, w.q, w.v, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
         } else if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
         if (h->d_tlog) h->tlog_used++;

@@ -238,6 +238,12 @@ int srbm_wb_plant_set_bodies_each(srbm_batch*, double*, double*, double*)
 int srbm_wb_forward_dynamics(srbm_batch*, double*, double*, double*, int*, double*, int*)
 int srbm_wb_forward_dynamics_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_wb_fd_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_wb_plant_set_ground(srbm_batch*, double*)
+int srbm_wb_plant_get_contact_state(srbm_batch*, double*)
+int srbm_wb_plant_set_contact_state(srbm_batch*, double*)
+int srbm_wb_ground_dynamics(srbm_batch*, double*, double*, double*, double*, double*, double*, int*)
+int srbm_wb_ground_dynamics_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_wb_ground_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

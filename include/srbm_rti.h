@@ -572,10 +572,17 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *       57      the plant kind (1)
  *       58      number of joints whose torque was clamped
  *       59      max_j |tau_j - tau_ff,j|: what the PD loop and the limits changed
- *       60      the smallest vertical plant force over the stance feet, 0 with none; negative: the held foot pulls (the plant's stated limit)
+ *       60      the smallest vertical plant force over the stance feet, 0 with none; negative: the held foot pulls (the plant's stated limit
+ *               without a ground)
  *       61      |a_plant - a_QP|_inf over the 18 accelerations
  *       62      |F_plant - F_QP|_inf over the stance feet
  *       63      0
+ *     Plant kind 1 with a ground set (srbm_wb_plant_set_ground, below), 58..63 from the LAST sub-step of the tick: 57..59 as above, and
+ *       60      the smallest vertical ground force over the feet the plan holds in stance, 0 if it holds none; >= 0 by construction
+ *       61      |a_plant - a_QP|_inf over the 18 accelerations
+ *       62      |F_ground - F_QP|_inf over all four feet, the QP's force zero for a foot out of the plan (as in fields 31..42)
+ *       63      4096 + word.  Bit i: foot i in ground contact; bit 4 + i: foot i slipping; bit 8 + i: the plan's contact flag of foot i
+ *               (field 43 + i) differs from the ground's
  *     Fields 31..42 and 51..56 are the QP's forces and acceleration for either kind.
  * The entries have the semantics of their srbm_step_log_* counterparts: srbm_tick_log_enable allocates max_ticks x batch records and sets the cursor to
  * 0 (0 disables and frees); capacity is checked before anything is launched; get (host, synchronous) and copy_dev (on the stream) fail for a slot
@@ -633,6 +640,57 @@ int srbm_wb_forward_dynamics_dev(srbm_batch* h, const double* q_dev, const doubl
  * else in it changes.  srbm_batch_clone carries the kind, the actuators, the sub-steps and the bodies. */
 int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* control_dev, const int* contact_dev,
                         const int* status_dev, double* sol_dev);
+
+/* ---- a compliant ground for the torque-driven plant ----
+ * The torque-driven plant above holds the PLANNED stance feet wherever they are, and a held foot pulls.  A ground is a SETTING of plant kind 1 (not a
+ * kind of its own): with one set the plant holds no foot.  Each foot meets a horizontal plane per instance that pushes and never pulls, with
+ * stick / slip Coulomb friction, found from the plant's own foot positions.  ground[batch][8] per instance:
+ *     0  ground height z0             finite, or -inf: no ground for this instance
+ *     1  normal stiffness k_n         > 0             2  normal damping d_n          >= 0
+ *     3  friction coefficient mu      >= 0
+ *     4  tangential stiffness k_t     > 0             5  tangential damping d_t      >= 0
+ *     6, 7  reserved                  must be 0
+ * The contact state cs[batch][12] holds per foot {in_contact (0 | 1), anchor_x, anchor_y}.  Per sub-step of h / S on the plant's current (q, v):
+ *     tau          the torque law of kind 1, unchanged (actuators off for a zero control action)
+ *     p_i, w_i     foot i: world position from the forward kinematics of q (the batch's leg geometry), world velocity w_i = J_i v with the
+ *                  LOCAL_WORLD_ALIGNED linear Jacobian J_i
+ *     delta = z0 - p_z
+ *     if !(delta > 0):  F_i = 0, in_contact = 0, anchor = (0, 0)
+ *     else:  if the foot was not in contact after the previous sub-step: anchor = (p_x, p_y)
+ *            N   = max(0, k_n delta - d_n w_z)
+ *            T0  = -k_t (p_xy - anchor) - d_t w_xy,   lim = mu N,   n0 = sqrt(T0x^2 + T0y^2)
+ *            n0 <= lim:  T = T0                        (stick)
+ *            else:       T = (lim / n0) T0             (slip),  anchor = p_xy + (T + d_t w_xy) / k_t
+ *            F_i = (T_x, T_y, N), in_contact = 1
+ *     M a = S' tau - C v - g + sum_i J_i' F_i          on the plant's own bodies: 18 unknowns, no constraint rows, solved exactly (LDL' of M)
+ *     v <- v + (h / S) a,  q <- pinocchio::integrate(q, v, h / S);  the push where kind 1 applies it
+ * cs is carried from sub-step to sub-step and, in the batch, from tick to tick.  A sub-step whose factorisation meets a pivot that is not finite or not
+ * positive takes a = 0 and reports (a, F) = 0 (flags bit 3 of the tick); its contact state is what the law left.
+ * What it is NOT: compliant, not rigid (a foot that carries N sinks by N / k_n); no impact law; no LCP; no terrain but one horizontal plane per
+ * instance; and the controller keeps believing its plan (no AdjustForCurrentContacts): tick log fields 43..46 against field 63 show where the plan and
+ * the ground disagree.
+ *
+ * srbm_wb_plant_set_ground: ground[batch][8]; NULL removes the ground, kind 1 is then the held-feet plant again.  Kind 0 ignores a ground.  Refused,
+ * naming the instance and the field, the batch untouched: a field that is not finite (z0 may be -inf) or outside its range; a reserved field != 0.
+ * srbm_wb_plant_get_contact_state / _set_contact_state: cs[batch][12] of the batch (after srbm_wb_plant_set_state, which resets it to "no foot in
+ * contact"); set refuses an in_contact other than 0 or 1 and an anchor that is not finite.  srbm_batch_clone carries the ground and the contact state. */
+int srbm_wb_plant_set_ground(srbm_batch* h, const double* ground);
+int srbm_wb_plant_get_contact_state(srbm_batch* h, double* cs);
+int srbm_wb_plant_set_contact_state(srbm_batch* h, const double* cs);
+/* The law and the solve alone: q[batch][19], v[batch][18], tau[batch][12], cs_in[batch][12] -> sol[batch][30] = a[18] then F[4][3] in foot order, zero
+ * for a foot in the air; cs_out[batch][12]; status[batch] (may be NULL) 0, or 1 for a factorisation breakdown (sol is then 0).  Refused without a
+ * ground, leg kinematics or bodies. */
+int srbm_wb_ground_dynamics(srbm_batch* h, const double* q, const double* v, const double* tau, const double* cs_in, double* sol, double* cs_out, int* status);
+/* ... on device pointers: one launch on the batch's stream, no copy, no synchronisation */
+int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* tau_dev, const double* cs_in_dev, double* sol_dev,
+                                double* cs_out_dev, int* status_dev);
+/* The ground step of tick `tick` on the caller's device arrays, the counterpart of srbm_wb_fd_step_dev: q_dev[batch][19], v_dev[batch][18],
+ * cs_dev[batch][12] in place from control_dev[batch][36] and status_dev[batch][2] as srbm_control_tick_dev returned them (the plan's contact flags
+ * are not an input); sol_dev (may be NULL) [batch][30] <- (a, F) of the last sub-step.  One launch on the batch's stream; never logs.  Refused
+ * without a ground, actuators, leg kinematics or bodies.
+ * srbm_controller_advance launches this kernel on the batch's (q, v, cs) when the kind is 1 and a ground is set; nothing else in it changes. */
+int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, double* cs_dev, const double* control_dev,
+                            const int* status_dev, double* sol_dev);
 
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */

@@ -7,6 +7,9 @@ medians and spreads.
   (d) torque     srbm_controller_advance with the torque-driven plant (srbm_wb_plant_set_kind 1: PD 20 / 0.5, the configured torque bounds as
                  limits, the controller's bodies), logged, S = 1 and S = 4 sub-steps per tick; beside (a) this is what the plant kind costs.  And
                  its step kernel alone (srbm_wb_fd_step_dev, S = 1 and 4), as (c)
+  (e) ground     (d) with a compliant ground set (srbm_wb_plant_set_ground: k_n 2e4, d_n 100, mu 0.7, k_t 1e4, d_t 50, the plane 3 mm above each
+                 instance's lowest foot at the start), logged, S = 1 and 4; beside (d) this is what the ground costs.  And its step kernel alone
+                 (srbm_wb_ground_step_dev, S = 1 and 4), as (c)
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -21,10 +24,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from srbm_loader import host
 from srbm_loader.control_tick import ControlTick
-from srbm_loader.controller_rollout import ControllerRollout, TICK_LOG_FIELDS, TORQUE_PLANT_LOG_FIELDS, FLAG_COAST, FLAG_BREAKDOWN, PLANT_TORQUE_DRIVEN
+from srbm_loader.controller_rollout import (ControllerRollout, TICK_LOG_FIELDS, TORQUE_PLANT_LOG_FIELDS, GROUND_PLANT_LOG_FIELDS, FLAG_COAST, FLAG_BREAKDOWN,
+                                            PLANT_TORQUE_DRIVEN, decode_ground_word)
 from srbm_loader.workloads import config_b_instance, instances
 
 F = dict(TICK_LOG_FIELDS, **TORQUE_PLANT_LOG_FIELDS)
+G = dict(TICK_LOG_FIELDS, **GROUND_PLANT_LOG_FIELDS)
 B, TICKS, TPU, DT, LIMIT_S = 256, 200, 50, 1e-3, 60.0
 RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 
@@ -38,7 +43,9 @@ def main():
     base = host.BatchMPC.cold_start(cfg, states, ees)
     q_init = np.tile(np.array(cfg['init_config'], float), (B, 1))
     q0, v0, _, st = base.clone().get_targets_from_traj(0.0, q_init)          # the plant starts on the targets of tick 0
-    res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': [], 'torque_s1_logged': [], 'torque_s4_logged': [], 'fd_step_s1': [], 'fd_step_s4': []}
+    res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': [], 'torque_s1_logged': [], 'torque_s4_logged': [], 'fd_step_s1': [], 'fd_step_s4': [],
+           'ground_s1_logged': [], 'ground_s4_logged': [], 'ground_step_s1': [], 'ground_step_s4': []}
+    ground = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
     f64 = dict(dtype=torch.float64, device='cuda')
@@ -82,11 +89,35 @@ def main():
             res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
             log = R.tick_log()
             info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
-                              zero_action_ticks=int((log[:, :, F['qp_status']] > 1).sum()),
+                              zero_action_ticks=int((log[:, :, F['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, F['qp_iters']].mean()),
                               breakdown_ticks=int(((log[:, :, F['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
                               clamped_ticks=int((log[:, :, F['clamped_joints']] > 0).sum()), min_stance_fz=float(log[:, :, F['min_stance_fz']].min()),
                               pulling_ticks=int((log[:, :, F['min_stance_fz']] < 0).sum()),
                               median_accel_mismatch=float(np.median(log[:, :, F['accel_mismatch']])), max_accel_mismatch=float(log[:, :, F['accel_mismatch']].max()))
+            if ground is None:          # the plane 3 mm above each instance's lowest foot of the first tick
+                ground = np.zeros((B, 8))
+                ground[:, 0] = log[0][:, F['foot_heights']].min(axis=1) + 0.003
+                ground[:, 1:6] = [2e4, 100.0, 0.7, 1e4, 50.0]
+        # (e) ... on its ground
+        for S in (1, 4):
+            name = 'ground_s%d_logged' % S
+            g, R = fresh(TICKS + 3)
+            R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, S)
+            R.set_ground(ground)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log = R.tick_log()
+            word = decode_ground_word(log[:, :, G['ground_word']])
+            info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
+                              zero_action_ticks=int((log[:, :, G['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, G['qp_iters']].mean()),
+                              breakdown_ticks=int(((log[:, :, G['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
+                              clamped_ticks=int((log[:, :, G['clamped_joints']] > 0).sum()),
+                              min_planned_stance_fz=float(log[:, :, G['min_planned_stance_fz']].min()),
+                              feet_in_contact_mean=float(word['in_contact'].sum(axis=-1).mean()), slipping_feet_mean=float(word['slipping'].sum(axis=-1).mean()),
+                              feet_off_the_plan_mean=float(word['plan_differs'].sum(axis=-1).mean()),
+                              median_accel_mismatch=float(np.median(log[:, :, G['accel_mismatch']])))
         # (b) the same loop from the host, on torch's buffers, on the batch's stream
         g, R = fresh()
         T = ControlTick(g)
@@ -129,6 +160,21 @@ def main():
                 fd_step()
                 signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
                 res['fd_step_s%d' % S].append(timed(g, fd_step))
+
+            # ... and the ground step kernel alone
+            R.set_ground(ground)
+            cs_d = torch.zeros((B, 12), **f64)
+            for S in (1, 4):
+                R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, S)
+                q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64)); cs_d.zero_()
+
+                def ground_step():
+                    for k in range(TICKS):
+                        R.ground_step_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), cs_d.data_ptr(), ctl_d.data_ptr(), st_d.data_ptr())
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                ground_step()
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                res['ground_step_s%d' % S].append(timed(g, ground_step))
     signal.setitimer(signal.ITIMER_REAL, 0)
     med = {k: float(np.median(v)) for k, v in res.items()}
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
