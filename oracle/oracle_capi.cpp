@@ -64,6 +64,14 @@ void* orc_mpc_clone(void* p) {
     return h;
 }
 const char* orc_mpc_error(void* p) { return static_cast<OrcMPC*>(p)->err.c_str(); }
+// the three cost setters of the caller, each with its own argument (orc_mpc_create gives all three the config's diagonal Q): full 12 x 12 row-major
+// Q and Phi, the final cost's linear term on its own.  A clone keeps them (they are members of the copied object).
+void orc_mpc_set_costs(void* p, const double* des12, const double* Q144, const double* Phi144, const double* Phi_w12) {
+    auto* h = static_cast<OrcMPC*>(p);
+    h->mpc->AddQuadraticTrackingCost(des12, Q144);
+    h->mpc->SetQuadraticFinalCost(Phi144);
+    h->mpc->SetLinearFinalCost(Phi_w12);
+}
 
 void orc_mpc_set_warmstart(void* p, const double* state13) {
     auto* h = static_cast<OrcMPC*>(p);

@@ -10,6 +10,7 @@ import numpy as np
 
 from gpu_kit import REL_TOL, advance, assert_bitwise, relerr, snapshot
 from gpu_kit import status_four_classes as cls
+from cost_variants_kit import install
 from oracle_py import OracleMPC
 from srbm_loader import host
 from srbm_loader.workloads import instances
@@ -63,22 +64,29 @@ def run_case(cfg, make_inst, B, steps, mode, splits, large=None, closed=False, p
     return dict(counters=d, n_cu=n_cu, queued_launches=queued_launches, kernel=info['kernel'], sizes=[r['sizes'] for r in ref], err=[r['err'] for r in ref])
 
 
-def make_batch(cfg, states, ees, step_rule=True, large=None):
+def make_batch(cfg, states, ees, step_rule=True, large=None, costs=None):
+    """costs: one (des, Q, Phi, Phi_w) per instance (tests/cost_variants_kit.py), installed on the device through the three _each setters and on
+    the oracles through set_costs; None: the costs of the constructors"""
     B = len(states)
     g = host.BatchMPC.cold_start(cfg, states, ees, large=large, initial_run=False)
+    if costs is not None:
+        assert len(costs) == B
+        install(g, 0, costs)
     assert g.solver_step_rule() == (0.0, 0.0)   # a new batch: exactly the reference's criterion (gap 1e-15), include/srbm_rti.h
     if step_rule:
         g.enable_fast_termination()             # bench.py's step_rule_mode: tol_step 1e-5, start_mu 0.1 (the latter acts in srbm_rti_advance only)
     oracles = []
     for b in range(B):
         o = OracleMPC(cfg)
+        if costs is not None:
+            o.set_costs(*costs[b])
         o.set_warmstart(states[b])
         oracles.append(o)
     return g, oracles
 
 
 def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=True, min_alive=None, fused=False, large=None, x_tol=REL_TOL, start_mu=None,
-                    qp_extra=(), contact_phase=None):
+                    qp_extra=(), contact_phase=None, costs=None):
     """cold start on both sides, then `steps` open-loop RTI steps (test/gait_opt_playground.cpp:113-126) with the device
     re-synchronised to the oracle before every step; returns per-step statistics.  Asserts entry-wise parity.
     fused=False: the device steps through srbm_get_real_time_update (host-pointer entry, one launch per phase: the lower-start attempt is
@@ -86,11 +94,12 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
     spline feet of the installed trajectory as its inputs and, with start_mu > 0, begins every solve with the lower-start ATTEMPT.
     The assembled QP and the duals are compared at the steps i % qp_every == 0 and at the steps in qp_extra; primal and states at every step.
     contact_phase: after the cold start the oracles' contact times are set that far apart (as many per foot as they have); the device takes the
-    schedule over with the first installed trajectory."""
+    schedule over with the first installed trajectory.
+    costs: per-instance cost sets (make_batch); the result then also tells the instances apart (x_compared_each, worst_each)."""
     B = len(states)
     N = cfg['num_nodes']
     dt = cfg['integrator_dt']
-    g, oracles = make_batch(cfg, states, ees, step_rule, large)
+    g, oracles = make_batch(cfg, states, ees, step_rule, large, costs)
     if start_mu is not None:
         g.set_solver_step_rule(g.solver_step_rule()[0], start_mu)
     x_by_step = []
@@ -111,6 +120,8 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
                                                dual_obj=0.0, kkt=0.0)
     n_cert = 0
     n_xcmp = 0
+    xcmp_each = np.zeros(B, int)
+    worst_each = [dict() for _ in range(B)]
     seen_shapes = set()          # (n, n_force) of the compared solves
     n_inacc = 0
     n_atz = 0
@@ -280,7 +291,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
         res = list(pool.map(check, range(B)))
         xs_ = np.array([r.get('x', 0.0) for r in res])
         x_by_step.append((float(xs_.max()), int(xs_.argmax()), int((xs_ > REL_TOL).sum())))
-        for r in res:
+        for b, r in enumerate(res):
             if r.get('dead'):
                 n_gave_up += r.get('gave_up', 0); n_gave_up_cert += r.get('gave_up_cert', 0)
                 worst['x_cert_gpu_where_oracle_gave_up'] = max(worst['x_cert_gpu_where_oracle_gave_up'], r.get('x_cert_gpu_where_oracle_gave_up', 0.0))
@@ -289,6 +300,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
             exact_status += r['exact']
             seen_sizes.add(r['n']); seen_shapes.add((r['n'], r['nf'])); seen_td += r['ntd'] > 0
             n_xcmp += r.get('x_compared', 0)
+            xcmp_each[b] += r.get('x_compared', 0)
             n_unique += r.get('z_unique', 0)
             n_cert += r.get('cert', 0)
             n_inacc += r.get('inacc', 0)
@@ -298,6 +310,7 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
             for k in worst:
                 if k in r:
                     worst[k] = max(worst[k], r[k])
+                    worst_each[b][k] = max(worst_each[b].get(k, 0.0), r[k])
         # foot-box size (info_.ee_box_size, grown / shrunk by the status of each solve): same on both sides
         for b in (0, B // 2, B - 1):
             if alive[b]:
@@ -309,4 +322,4 @@ def resync_protocol(cfg, states, ees, steps, qp_every=1, pool=None, step_rule=Tr
         assert ctr['low_tried'] >= 0.8 * ctr['solves'], ctr
     # (a device SolvedInacc where the oracle says Solved is a CLASSIFICATION difference of two interior-point codes at the fp64 floor -- observed on 13 of
     #  5 102 host-driven solves, all within 6e-11 of the oracle's minimiser; every such pair is held to the full bound above and listed in the result)
-    return dict(inacc=n_inacc, inacc_where=inacc_where, duals_compared_on_row_space=n_atz, oracle_gave_up=n_gave_up, device_certified_where_oracle_gave_up=n_gave_up_cert, x_by_step=x_by_step, counters=ctr, alive=int(alive.sum()), sizes=seen_sizes, shapes=seen_shapes, x_compared=n_xcmp, td_steps=seen_td, worst=worst, exact_status=exact_status, total=total, z_unique=n_unique, certified=n_cert)
+    return dict(inacc=n_inacc, inacc_where=inacc_where, duals_compared_on_row_space=n_atz, oracle_gave_up=n_gave_up, device_certified_where_oracle_gave_up=n_gave_up_cert, x_by_step=x_by_step, counters=ctr, alive=int(alive.sum()), sizes=seen_sizes, shapes=seen_shapes, x_compared=n_xcmp, x_compared_each=xcmp_each, worst_each=worst_each, td_steps=seen_td, worst=worst, exact_status=exact_status, total=total, z_unique=n_unique, certified=n_cert)

@@ -38,6 +38,7 @@ void* orc_mpc_create(orc_config*)
 void orc_mpc_destroy(void*)
 void* orc_mpc_clone(void*)
 char* orc_mpc_error(void*)
+void orc_mpc_set_costs(void*, double*, double*, double*, double*)
 void orc_mpc_set_warmstart(void*, double*)
 int orc_mpc_initial_run(void*, double*, double*)
 int orc_mpc_solve(void*, double*, double, double*)
@@ -159,6 +160,11 @@ class OracleMPC:
         if rc < 0:
             raise RuntimeError(self.L.orc_mpc_error(self.h).decode())
         return rc
+
+    def set_costs(self, des, Q, Phi, Phi_w):
+        """AddQuadraticTrackingCost(des, Q), SetQuadraticFinalCost(Phi), SetLinearFinalCost(Phi_w): full 12 x 12 matrices, the final cost its own"""
+        a = [np.ascontiguousarray(v, dtype=np.float64).reshape(k) for v, k in ((des, 12), (Q, 144), (Phi, 144), (Phi_w, 12))]
+        self.L.orc_mpc_set_costs(self.h, _d(a[0]), _d(a[1]), _d(a[2]), _d(a[3]))
 
     def set_warmstart(self, state13):
         s = np.ascontiguousarray(state13, dtype=np.float64)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import lp_reference
+from cost_variants_kit import cost_set, install
 from gpu_kit import REL_TOL, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
@@ -13,15 +14,20 @@ from srbm_loader.workloads import EE_NOMINAL, config_c_instance, instances
 pytestmark = pytest.mark.gpu
 
 
-def run_pair(cfgname, nsteps, batch=2, tol=1e-15, large=False):
-    """GPU batch + oracle brought to the same point of an open-loop RTI run (test/gait_opt_playground.cpp:113-126)"""
+def run_pair(cfgname, nsteps, batch=2, tol=1e-15, large=False, costs=None):
+    """GPU batch + oracle brought to the same point of an open-loop RTI run (test/gait_opt_playground.cpp:113-126)
+    costs: a (des, Q, Phi, Phi_w) of tests/cost_variants_kit.py, installed on every instance of the batch and on the oracle before the cold start"""
     cfg = load_config(cfgname)
     s0 = np.array(cfg['srb_init'], float)
     g = host.BatchMPC(cfg, batch, large=large)
+    if costs is not None:
+        install(g, 0, [costs] * batch)
     g.set_state_trajectory_warm_start(s0)
     g.set_solver_tolerances(tol, tol, 1e-10, 200)
     g.set_solver_step_rule(0.0, 0.0)        # the caller drives the protocol here: the solves it differentiates run to the gap criterion (include/srbm_rti.h)
     o = OracleMPC(cfg)
+    if costs is not None:
+        o.set_costs(*costs)
     o.set_warmstart(s0)
     g.create_initial_run(s0, EE_NOMINAL); o.initial_run(s0, EE_NOMINAL)
     dt = cfg['integrator_dt']
@@ -96,30 +102,14 @@ def as_coded_sensitivity(A, P, q, xs, z, s, nx, mi):
     return sol, live, lam
 
 
-@pytest.mark.parametrize('cfgname,nsteps,large', [('a1_configuration', 3, False), ('a1_configuration', 8, False), ('a1_gait_opt_config', 2, False),
-                                                  ('a1_configuration', 3, True)],
-                         ids=['a1_configuration-3', 'a1_configuration-8', 'a1_gait_opt_config-2', 'a1_configuration-3-large'])
-def test_kkt_sensitivity(cfgname, nsteps, large):
-    """a12: d = [dz; dlam; dnu] of clarabel_interface.cpp:262-612 (as coded, +diag(s)).  The device solves it in the
-    condensed coordinates; (1) that must equal the full-space system solved densely in numpy on the SAME QP, solution
-    and multipliers (tight); (2) against the oracle only the well-posed parts are compared: with exact complementarity
-    the system's solution is (0, 1, nu), what remains is -s_i on degenerate rows (lambda_i and s_i both ~ sqrt(mu)),
-    whose size is a property of the interior-point path of each solver, not of the QP.
-    large: the LARGE build keeps a 112 x 112 block of the LU in LDS; at n_u = 120 the first eight elimination steps run on the copy in L2 and
-    the last eight rows of the back substitution are block-wide dot products -- the path no standard-build configuration takes.  Part (1) and
-    a factorisation that did not fail; part (2) stays with the standard build."""
-    cfg, g, o, state, ee, t = run_pair(cfgname, nsteps, large=large)
-    assert o.stats()['status'] == 0 and g.status()[0][0] == 0
-    assert o.gait_gradient() is not None
-    do = o.gait_d()
-    gait = host.BatchGaitOptimizer(g)
+def sensitivity_solves_its_own_system(cfg, g, o, gait):
+    """part (1) of test_kkt_sensitivity: the device's d against the dense full-space solve on the device's own exported QP, solution and
+    multipliers, and the residuals of the three block rows; returns (dz, dlam, dnu, live rows, lambda, lambda o dlambda, x*)"""
     gait.compute_sensitivity()
     d = gait.sensitivity()
     sz = o.sizes()
     n, mi, me = sz['n'], sz['n_ineq'], sz['n_eq']
     nx = (cfg['num_nodes'] + 1) * 12
-    if large:
-        assert n - nx > 112              # n_u beyond KG_LMAX of the LARGE build (csrc/srbm_gait_sens.hiph): the L2 steps run
     assert np.array_equal(d[0], d[1])
     dz, dl, dn = d[0, :n], d[0, n:n + mi], d[0, n + mi:n + mi + me]
     # (1) same linear system, same data, dense full-space solve
@@ -144,11 +134,11 @@ def test_kkt_sensitivity(cfgname, nsteps, large):
     assert np.abs(r1).max() <= 1e-5 * max(1.0, np.abs(dldx).max())
     assert np.abs(G @ dz + s[0, ineq] * dl)[live].max() <= 1e-9
     assert np.abs(Ae @ dz).max() <= 1e-9
-    if large:
-        gait.compute_gradient()
-        assert gait.gradient()[1][0] == 1       # valid: among its conditions lu_fail == 0
-        return
-    # (2) oracle: dq = dz + x*, dh = -lam o dlam, db = -dnu (the QP partials the gradient is built from)
+    return dz, dl, dn, live, lam, mu_g, xg
+
+
+def sensitivity_against_oracle(label, o, do, nx, n, mi, dz, dn, mu_g, xg, live):
+    """the figures of part (2) of test_kkt_sensitivity, printed: (dq, dh per inequality row, db) of the device against the oracle's d"""
     xo = o.x(); lam_o = o.z()[nx:nx + mi]
     s_o = o.s()[nx:nx + mi]
     e_dq = relerr(dz + xg, do[:n] + xo)
@@ -158,12 +148,70 @@ def test_kkt_sensitivity(cfgname, nsteps, large):
     # ratio of two rounding-level numbers, a property of where each interior-point path stopped, not of the QP
     thr = 1e-5 * max(1.0, np.abs(lam_o).max())
     degenerate = (lam_o < thr) & (s_o < thr)
-    # (with both sides on the same QP and the reference's 1e-15 gap tolerance even those rows agree: asserted for ALL live rows)
-    print('sensitivity vs oracle [%s, %d]: dq %.1e  dh (non-degenerate rows) %.1e  dh (degenerate rows: %d) %.1e  db %.1e' %
-          (cfgname, nsteps, e_dq, dmu[live & ~degenerate].max(), (live & degenerate).sum(), dmu[live & degenerate].max() if (live & degenerate).any() else 0.0, e_dn))
+    print('sensitivity vs oracle [%s]: dq %.1e  dh (non-degenerate rows) %.1e  dh (degenerate rows: %d) %.1e  db %.1e' %
+          (label, e_dq, dmu[live & ~degenerate].max(), (live & degenerate).sum(), dmu[live & degenerate].max() if (live & degenerate).any() else 0.0, e_dn))
+    return e_dq, dmu, e_dn
+
+
+@pytest.mark.parametrize('cfgname,nsteps,large', [('a1_configuration', 3, False), ('a1_configuration', 8, False), ('a1_gait_opt_config', 2, False),
+                                                  ('a1_configuration', 3, True)],
+                         ids=['a1_configuration-3', 'a1_configuration-8', 'a1_gait_opt_config-2', 'a1_configuration-3-large'])
+def test_kkt_sensitivity(cfgname, nsteps, large):
+    """a12: d = [dz; dlam; dnu] of clarabel_interface.cpp:262-612 (as coded, +diag(s)).  The device solves it in the
+    condensed coordinates; (1) that must equal the full-space system solved densely in numpy on the SAME QP, solution
+    and multipliers (tight); (2) against the oracle only the well-posed parts are compared: with exact complementarity
+    the system's solution is (0, 1, nu), what remains is -s_i on degenerate rows (lambda_i and s_i both ~ sqrt(mu)),
+    whose size is a property of the interior-point path of each solver, not of the QP.
+    large: the LARGE build keeps a 112 x 112 block of the LU in LDS; at n_u = 120 the first eight elimination steps run on the copy in L2 and
+    the last eight rows of the back substitution are block-wide dot products -- the path no standard-build configuration takes.  Part (1) and
+    a factorisation that did not fail; part (2) stays with the standard build."""
+    cfg, g, o, state, ee, t = run_pair(cfgname, nsteps, large=large)
+    assert o.stats()['status'] == 0 and g.status()[0][0] == 0
+    assert o.gait_gradient() is not None
+    do = o.gait_d()
+    gait = host.BatchGaitOptimizer(g)
+    sz = o.sizes()
+    n, mi, me = sz['n'], sz['n_ineq'], sz['n_eq']
+    nx = (cfg['num_nodes'] + 1) * 12
+    if large:
+        assert n - nx > 112              # n_u beyond KG_LMAX of the LARGE build (csrc/srbm_gait_sens.hiph): the L2 steps run
+    dz, dl, dn, live, lam, mu_g, xg = sensitivity_solves_its_own_system(cfg, g, o, gait)
+    if large:
+        gait.compute_gradient()
+        assert gait.gradient()[1][0] == 1       # valid: among its conditions lu_fail == 0
+        return
+    # (2) oracle: dq = dz + x*, dh = -lam o dlam, db = -dnu (the QP partials the gradient is built from)
+    e_dq, dmu, e_dn = sensitivity_against_oracle('%s, %d' % (cfgname, nsteps), o, do, nx, n, mi, dz, dn, mu_g, xg, live)
+    # (with both sides on the same QP and the reference's 1e-15 gap tolerance even the degenerate rows agree: asserted for ALL live rows)
     assert e_dq < REL_TOL
     assert dmu[live].max() < REL_TOL
     assert e_dn < REL_TOL
+
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_kkt_sensitivity_with_a_final_cost_of_its_own(name):
+    """part (1) of test_kkt_sensitivity under cost sets A and B of tests/cost_variants_kit.py (Phi, Phi_w not Q, w; B: full matrices), installed
+    on both sides before the cold start: the right-hand side of the sensitivity system takes the last node's cost from Phi and Phi_w
+    (csrc/srbm_gait_sens.hiph), which no other batch of the suite tells from Q and w.  Part (2) and dH/dtheta are printed, not asserted: with
+    these costs the oracle's own gradient has entries of 1e12 ... 1e19 on rows decided by the interior-point path
+    (test_gradient_entries_that_depend_on_the_interior_point_path)."""
+    cfgname, nsteps = 'a1_configuration', 3
+    cfg, g, o, state, ee, t = run_pair(cfgname, nsteps, costs=cost_set(load_config(cfgname), name))
+    assert o.stats()['status'] == 0 and g.status()[0][0] == 0
+    _, _, P, q = g.export_qp(0)
+    _, _, Po, qo = o.qp_dense()
+    assert max(np.abs(P - Po).max(), np.abs(q - qo).max()) <= 1e-12          # the costs are installed on both sides
+    nx = (cfg['num_nodes'] + 1) * 12
+    assert np.abs(P[nx - 12:nx, nx - 12:nx] - P[:12, :12]).max() > 1.0 and np.abs(q[nx - 12:nx] - q[:12]).max() > 1.0
+    gait = host.BatchGaitOptimizer(g)
+    dz, dl, dn, live, lam, mu_g, xg = sensitivity_solves_its_own_system(cfg, g, o, gait)
+    sz = o.sizes()
+    go = o.gait_gradient()
+    if go is not None:
+        sensitivity_against_oracle('%s, %d, cost set %s' % (cfgname, nsteps, name), o, o.gait_d(), nx, sz['n'], sz['n_ineq'], dz, dn, mu_g, xg, live)
+        gait.compute_gradient()
+        gg, valid = gait.gradient()
+        print('dH/dtheta [cost set %s]: valid %d, device largest entry %.3g, oracle largest entry %.3g' % (name, valid[0], np.abs(gg[0]).max(), np.abs(go).max()))
 
 
 @pytest.mark.parametrize('cfgname,nsteps', [('a1_configuration', 3), ('a1_configuration', 8), ('a1_configuration', 13),

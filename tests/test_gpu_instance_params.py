@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from closed_loop_kit import chip_cu_count
+from cost_variants_kit import cost_set, install, spd
 from gpu_kit import REL_TOL, assert_rows_bitwise, relerr
 from oracle_py import OracleMPC, load_config
 from srbm_loader import host
@@ -35,10 +36,13 @@ def het_configs(B, seed=4242, num_nodes=None):
 
 def full_q(cfg):
     """a full symmetric positive-definite Q around the config's diagonal (fixed seed)"""
-    rng = np.random.Generator(np.random.MT19937(99))
-    d = np.sqrt(np.asarray(cfg['Q_srbd_diag'], float))
-    R = rng.uniform(-0.2, 0.2, (12, 12))
-    return np.diag(d) @ (np.eye(12) + R @ R.T) @ np.diag(d)
+    return spd(cfg, 99)
+
+
+def full_q_costs(cfg):
+    """(des, Q, Phi, Phi_w) of the full-Q instance, as setup() installs them"""
+    Q, des = full_q(cfg), host.manifold_to_tangent(cfg['srb_target'])
+    return des, Q, Q, -1 * Q @ des
 
 
 def inputs(cfgs):
@@ -48,10 +52,7 @@ def inputs(cfgs):
 def setup(g, mode, states, ees, full=()):
     """full: (index within g, cfg) pairs whose costs become the full-Q costs"""
     for k, cfg in full:
-        Q, des = full_q(cfg), host.manifold_to_tangent(cfg['srb_target'])
-        g.add_quadratic_tracking_cost_each(k, des[None], Q[None])
-        g.set_quadratic_final_cost_each(k, Q[None])
-        g.set_linear_final_cost_each(k, (-1 * Q @ des)[None])
+        install(g, k, [full_q_costs(cfg)])
     g.set_state_trajectory_warm_start(states)
     g.set_solver_tolerances(*host.REFERENCE_SOLVER_SETTINGS)
     g.set_solver_step_rule(*mode)
@@ -151,8 +152,11 @@ def test_heterogeneous_batch_matches_its_oracles_on_identical_inputs():
     B, steps = 32, 12
     cfgs = het_configs(B)
     states, ees = inputs(cfgs)
-    g = host.BatchMPC.cold_start(cfgs, states, ees, mode=(0.0, 0.0))          # (the oracle takes a diagonal Q: no full-Q instance here)
+    g = host.BatchMPC.cold_start(cfgs, states, ees, mode=(0.0, 0.0), initial_run=False)
+    install(g, FULL_Q_INST, [full_q_costs(cfgs[FULL_Q_INST])])               # the full-Q instance faces its oracle like every other
+    g.create_initial_run(states, ees)
     oracles = [OracleMPC(c) for c in cfgs]
+    oracles[FULL_Q_INST].set_costs(*full_q_costs(cfgs[FULL_Q_INST]))
     for b, o in enumerate(oracles):
         o.set_warmstart(states[b])
     pool = ThreadPoolExecutor(16)
@@ -237,10 +241,12 @@ def test_heterogeneous_closed_loop_matches_oracle_plant_and_batches_of_one():
     assert np.all(a['err'] == 0)
     dt = cfgs[0]['integrator_dt']
     for b in range(B):
-        if b != FULL_Q_INST:               # (the oracle takes a diagonal Q)
-            o = OracleMPC(cfgs[b]); o.set_warmstart(states[b]); o.initial_run(states[b], ees[b].reshape(4, 3))
-            x = o.plant_integrate(states[b], 0.0, dt, 1, 0)
-            assert relerr(first[b], x) < 1e-6, (b, relerr(first[b], x))
+        o = OracleMPC(cfgs[b])
+        if b == FULL_Q_INST:
+            o.set_costs(*full_q_costs(cfgs[b]))
+        o.set_warmstart(states[b]); o.initial_run(states[b], ees[b].reshape(4, 3))
+        x = o.plant_integrate(states[b], 0.0, dt, 1, 0)
+        assert relerr(first[b], x) < 1e-6, (b, relerr(first[b], x))
         one = make_one(cfgs, b, (0.0, 0.0))
         f1, s1, p1 = run(one, slice(b, b + 1))
         assert_rows_bitwise(a, b, s1, 0, 'closed loop')
@@ -326,9 +332,10 @@ def test_batch_wide_setters_after_each_setters_give_the_uniform_batch():
     u = host.BatchMPC(base, B)
     h = host.BatchMPC.from_configs(cfgs)
     h.add_force_cost_each(0, np.linspace(0, 1e-3, B))
-    Q, des = np.diag(np.asarray(base['Q_srbd_diag'], float)), host.manifold_to_tangent(base['srb_target'])
+    des, Q, Phi, Phi_w = cost_set(base, 'C')           # a final cost that is not the tracking cost (tests/cost_variants_kit.py): full Phi, its own target
+    assert not np.array_equal(Phi, Q) and not np.array_equal(Phi_w, -1 * Q @ des)
     for g in (u, h):
-        g.add_quadratic_tracking_cost(des, Q); g.set_quadratic_final_cost(Q); g.set_linear_final_cost(-1 * Q @ des); g.add_force_cost(5e-4)
+        g.add_quadratic_tracking_cost(des, Q); g.set_quadratic_final_cost(Phi); g.set_linear_final_cost(Phi_w); g.add_force_cost(5e-4)
         setup(g, (0.0, 0.0), states, ees)
         g.rti_advance(0, 3); g.synchronize()
     a, b = snap(u), snap(h)
