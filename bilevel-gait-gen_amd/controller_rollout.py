@@ -1,8 +1,11 @@
 """Whole-controller rollouts (include/srbm_rti.h: srbm_controller_advance, srbm_wb_plant_*, srbm_tick_log_*): the loop of the reference's top-level
 program (test/simulation_mpc.cpp:186-215) for every instance of a host.BatchMPC -- MPCController::ComputeControlAction every tick, an MPC update
 every `ticks_per_update` ticks, and between them a whole-body plant: by default the one that integrates the accelerations of the whole-body QP
-(it has no ground, no joint PD loop and no AdjustForCurrentContacts: the header says what that means), or, after set_plant(1, ...), the
-torque-driven one -- the constrained forward dynamics of the plant's own bodies under the returned torques, the joint PD loop and the torque limits.
+(it has no ground and no joint PD loop: the header says what that means), or, after set_plant(1, ...), the torque-driven one -- the constrained
+forward dynamics of the plant's own bodies under the returned torques, the joint PD loop and the torque limits.  With a ground under that plant
+(set_ground) the MPC update can be the reference's MPCUpdate in full: set_contact_feedback(True) runs MPC::AdjustForCurrentContacts on the ground's
+contact state before every update, and advance(..., gait=, gait_opt_freq=) branches every update into line search / update + gradient + LP / plain
+update (srbm_gait_controller_advance).  Without a ground nothing measures a contact, and there is no AdjustForCurrentContacts.
 A module of its own beside host.py, as control_tick.py and mpc_period.py are: it calls through the library `host.declare` has typed, and
 tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands.
 
@@ -13,7 +16,9 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.set_plant(1, kp, kd, limit, 4)      optional: the torque-driven plant, 4 sub-steps per tick; R.set_plant_bodies(...): its own bodies
     R.set_ground(ground)                  optional, with set_plant(1, ...): a compliant ground [batch][8] under the torque-driven plant's feet
     R.tick_log_enable(200)                optional: one record per tick and instance
+    R.set_contact_feedback(True)          optional, with a ground: early touch-downs re-time the plan before every MPC update
     R.advance(0, 200, 50, 1e-3)           200 ticks of 1 ms, an MPC update every 50; asynchronous
+    R.advance(0, 200, 50, 1e-3, gait=go, gait_opt_freq=5)      the same with the gait step of host.BatchGaitOptimizer `go` in the updates
     q, v = R.state(); log = R.tick_log()"""
 import ctypes as C
 
@@ -33,6 +38,7 @@ GROUND_PLANT_LOG_FIELDS = dict(plant_kind=57, clamped_joints=58, torque_deviatio
                                ground_word=63)
 GROUND_WORD_OFFSET = 4096
 GROUND_DOUBLES, CONTACT_STATE_DOUBLES = 8, 12
+CONTACT_FEEDBACK_DOUBLES = 8        # the feedback record of an instance: per foot {touch-downs moved, time of the last move (-1: none)}
 FLAG_PUSH, FLAG_UPDATE, FLAG_COAST, FLAG_BREAKDOWN = 1, 2, 4, 8
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
 
@@ -72,10 +78,38 @@ class ControllerRollout:
         m._chk(self.L.srbm_wb_plant_get_state(m.h, _d(q), _d(v)))
         return q, v
 
-    def advance(self, first_tick, ticks, ticks_per_update, tick_dt):
+    def advance(self, first_tick, ticks, ticks_per_update, tick_dt, gait=None, gait_opt_freq=None):
         """ticks first_tick .. first_tick + ticks - 1 of period tick_dt: control tick, plant step, and after every tick k > 0 with
-        k % ticks_per_update == 0 an MPC update at k * tick_dt that is in force from tick k + 1; asynchronous on the batch's stream"""
-        self.mpc._chk(self.L.srbm_controller_advance(self.mpc.h, int(first_tick), int(ticks), int(ticks_per_update), float(tick_dt)))
+        k % ticks_per_update == 0 an MPC update at k * tick_dt that is in force from tick k + 1; asynchronous on the batch's stream.
+        gait: a host.BatchGaitOptimizer of this batch -- update r = k / ticks_per_update is then a line search (r % gait_opt_freq == 0), an update
+        followed by gradient and LP ((r + 1) % gait_opt_freq == 0) or a plain update (srbm_gait_controller_advance)"""
+        if gait is None:
+            if gait_opt_freq is not None:
+                raise ValueError('gait_opt_freq without a gait optimiser')
+            self.mpc._chk(self.L.srbm_controller_advance(self.mpc.h, int(first_tick), int(ticks), int(ticks_per_update), float(tick_dt)))
+            return
+        if gait.mpc is not self.mpc:
+            raise ValueError('the gait optimiser belongs to another batch')
+        if gait_opt_freq is None:
+            raise ValueError('a gait optimiser without gait_opt_freq')
+        self.mpc._chk(self.L.srbm_gait_controller_advance(gait.g, int(first_tick), int(ticks), int(ticks_per_update), float(tick_dt), int(gait_opt_freq)))
+
+    # ---- contact feedback from the ground ----
+    def set_contact_feedback(self, on):
+        """MPC::AdjustForCurrentContacts on the ground's contact state before every MPC update of `advance` (which then requires the torque-driven
+        plant with a ground); off by default"""
+        self.mpc._chk(self.L.srbm_controller_set_contact_feedback(self.mpc.h, int(bool(on))))
+
+    def contact_feedback(self):
+        """-> fb[batch][4][2]: per foot the number of touch-downs moved since set_state and the time of the last move (-1: none)"""
+        m = self.mpc
+        fb = np.zeros((m.batch, 4, 2))
+        m._chk(self.L.srbm_controller_get_contact_feedback(m.h, _d(fb)))
+        return fb
+
+    def contact_feedback_dev(self, time, cs):
+        """the feedback kernel alone on device pointers (ints): time[batch], cs[batch][12]; asynchronous, counts in the feedback record"""
+        self.mpc._chk(self.L.srbm_controller_contact_feedback_dev(self.mpc.h, time, cs))
 
     def plant_step_dev(self, tick, tick_dt, q, v, qp_sol, status):
         """the plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from qp_sol[batch][30], status[batch][2] of

@@ -23,6 +23,7 @@
 #include "srbm_wb_plant.hiph"
 #include "srbm_wb_fd.hiph"
 #include "srbm_wb_ground.hiph"
+#include "srbm_contact_feedback.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
@@ -113,6 +114,9 @@ struct srbm_batch {
     // the ground of the torque-driven plant (srbm_wb_ground.hiph)
     double* d_ground = nullptr;      // [batch][WBG_GROUND_DOUBLES]; nullptr: no ground, kind 1 holds the planned feet (srbm_wb_plant_set_ground)
     double* d_cs = nullptr;          // the contact state [batch][WBG_CS_DOUBLES], allocated with d_wb
+    // contact feedback of the rollout's MPC update (srbm_contact_feedback.hiph)
+    int contact_fb = 0;              // 1: the update ticks of srbm_controller_advance run the feedback kernel (srbm_controller_set_contact_feedback)
+    double* d_fb = nullptr;          // the feedback record [batch][SRBM_FB_DOUBLES], allocated with d_wb
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -428,7 +432,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
-    (void)hipFree(h->d_ground); (void)hipFree(h->d_cs);
+    (void)hipFree(h->d_ground); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -458,6 +462,7 @@ static int wb_alloc(srbm_batch* h) {
     if (!h->d_wb) HIPCHK(hipMalloc(&h->d_wb, sizeof(double) * WB_DOUBLES * B));
     if (!h->d_wb_int) HIPCHK(hipMalloc(&h->d_wb_int, sizeof(int) * WB_INTS * B));
     if (!h->d_cs) HIPCHK(hipMalloc(&h->d_cs, sizeof(double) * WBG_CS_DOUBLES * B));
+    if (!h->d_fb) HIPCHK(hipMalloc(&h->d_fb, sizeof(double) * SRBM_FB_DOUBLES * B));
     return 0;
 }
 static int alloc_batch(srbm_batch* h, hipStream_t borrowed_stream) {
@@ -599,6 +604,9 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     if (ok && src->d_tick_q) ok = tick_alloc(h) == 0 && cp(h->d_tick_q, src->d_tick_q, sizeof(double) * 19 * B);
     // (... and the whole-body plant's (q, v); the tick log, like the step log, stays off)
     if (ok && src->d_wb) ok = wb_alloc(h) == 0 && cp(h->d_wb, src->d_wb, sizeof(double) * (19 + 18) * B) && cp(h->d_cs, src->d_cs, sizeof(double) * WBG_CS_DOUBLES * B);
+    // (... and the contact-feedback setting with its record)
+    h->contact_fb = src->contact_fb;
+    if (ok && src->d_wb) ok = cp(h->d_fb, src->d_fb, sizeof(double) * SRBM_FB_DOUBLES * B);
     // (... and the kind of the plant, its actuators, sub-steps and bodies)
     h->fd_kind = src->fd_kind; h->fd_substeps = src->fd_substeps;
     if (ok && src->d_fd_act)
@@ -2180,7 +2188,10 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     HIPCHK(hipMemcpyAsync(w.q, q, sizeof(double) * 19 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(w.v, v, sizeof(double) * 18 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_cs, 0, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch, h->stream));          // no foot in contact
-    return srbm_synchronize(h);
+    std::vector<double> fb(SRBM_FB_DOUBLES * (size_t)h->batch);                                                   // no touch-down moved
+    for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
+    HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);          // (fb is read until here)
 }
 int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
     if (!h) return fail("srbm_wb_plant_get_state: bad arguments");
@@ -2444,12 +2455,64 @@ int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_d
     if (use_batch(h)) return -1;
     return launch_wb_ground(h, tick, tick_dt, q_dev, v_dev, cs_dev, control_dev, nullptr, status_dev, nullptr, sol_dev, nullptr, nullptr);
 }
-int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt) {
-    const std::string fn = "srbm_controller_advance";
-    if (!h) return fail(fn + ": bad arguments (NULL handle)");
+// ---- contact feedback from the ground (srbm_contact_feedback.hiph) ----
+static int launch_contact_feedback(srbm_batch* h, const double* time, const double* cs) {
+    const int tot = h->batch * SRBM_NEE;
+    hipLaunchKernelGGL(srbm_k_contact_feedback, dim3((tot + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, time, cs, h->d_fb);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_controller_set_contact_feedback(srbm_batch* h, int on) {
+    if (!h) return fail("srbm_controller_set_contact_feedback: bad arguments");
+    if (on != 0 && on != 1) return fail("srbm_controller_set_contact_feedback: on " + std::to_string(on) + " (0: off, 1: on)");
+    h->contact_fb = on;
+    return 0;
+}
+int srbm_controller_get_contact_feedback(srbm_batch* h, double* fb) {
+    if (!h || !fb) return fail("srbm_controller_get_contact_feedback: bad arguments");
+    if (!h->d_wb) return fail(WB_NO_STATE);
+    return fetch(h, {{fb, h->d_fb, sizeof(double) * SRBM_FB_DOUBLES * (size_t)h->batch}});
+}
+int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, const double* cs_dev) {
+    if (!h || !time_dev || !cs_dev) return fail("srbm_controller_contact_feedback_dev: bad arguments");
+    if (!h->d_wb) return fail(WB_NO_STATE);
+    if (use_batch(h)) return -1;
+    return launch_contact_feedback(h, time_dev, cs_dev);
+}
+// MPCController::MPCUpdate's branch on the run number (mpc_controller.cpp:324-346) as srbm_gait_rti_advance has it, on the state, time and ee of
+// the tick (device arrays of the batch), with the record of the run where a step log is enabled
+static int gait_update(srbm_gait* g, int run, int F, const double* state, const double* time, const double* ee) {
+    srbm_batch* h = g->h;
+    const size_t B = h->batch;
+    if (run % F != 0 && (run + 1) % F != 0) {
+        if (srbm_get_real_time_update_dev(h, state, time, ee)) return -1;
+        launch_gait_ready(g, 0);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    HIPCHK(hipMemcpyAsync(h->d_state, state, sizeof(double) * 13 * B, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ee, ee, sizeof(double) * 12 * B, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_time, time, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream));
+    if (run % F == 0) {
+        // instances without a ready gradient get the plain update through the same 10-candidate batch (zero step)
+        if (line_search_core(g, true) || log_gait_step(g, SRBM_GAIT_RUN_LINE_SEARCH)) return -1;          // (logged before the flag is reset: it tells who searched)
+        launch_gait_ready(g, 0);
+    } else {
+        // the solve the gradient differentiates: to the gap criterion whatever the batch's step rule says (srbm_gait_rti_advance)
+        if (launch_step(h, true) || gait_opt_core(g) || log_gait_step(g, SRBM_GAIT_RUN_GRADIENT)) return -1;
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// The loop of srbm_controller_advance and srbm_gait_controller_advance.  g: nullptr, or the gait handle whose batch is h: the update after tick k
+// is then run k / ticks_per_update of the branch of srbm_gait_rti_advance.
+static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g, int first_tick, int ticks, int ticks_per_update, double tick_dt, int gait_opt_freq) {
     if (!h->d_wb) return fail(fn + ": the whole-body plant state has not been set (srbm_wb_plant_set_state)");
     if (tick_usable(h)) return -1;
     if (h->fd_kind == 1 && !h->d_fd_act) return fail(fn + ": " + FD_NO_ACTUATORS);
+    if (h->contact_fb && !(h->fd_kind == 1 && h->d_ground))
+        return fail(fn + ": contact feedback is on (srbm_controller_set_contact_feedback) and needs the torque-driven plant with a ground "
+                    "(srbm_wb_plant_set_kind 1, srbm_wb_plant_set_ground): without a ground nothing measures a contact");
     if (first_tick < 0 || ticks < 0 || ticks > INT_MAX - first_tick) return fail(fn + ": first_tick >= 0 and ticks >= 0 are required");
     if (ticks_per_update < 1) return fail(fn + ": ticks_per_update >= 1 is required");
     if (!std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(fn + ": a finite tick_dt > 0 is required");
@@ -2475,6 +2538,8 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
         double* const time = w.time + (k & 1) * B;
         const bool update = k > 0 && k % ticks_per_update == 0;
         if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
+        // mpc_controller.cpp:322: the contacts measured at t_k -- the ground's state after tick k - 1 -- re-time the plan the update starts from
+        if (update && h->contact_fb && launch_contact_feedback(h, time, h->d_cs)) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
         if (h->fd_kind == 1 && h->d_ground) {
             if (launch_wb_ground(h, k, tick_dt, w.q, w.v, h->d_cs, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
@@ -2483,9 +2548,21 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
         } else if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
         if (h->d_tlog) h->tlog_used++;
         // the hand-off of mpc_controller.cpp:142-156: the state and foot positions of THIS tick to the solve, the new trajectories in force from tick k + 1
-        if (update && srbm_get_real_time_update_dev(h, w.state, time, w.ee)) return -1;
+        if (update && !g && srbm_get_real_time_update_dev(h, w.state, time, w.ee)) return -1;
+        if (update && g && gait_update(g, k / ticks_per_update, gait_opt_freq, w.state, time, w.ee)) return -1;
     }
     return 0;
+}
+int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_per_update, double tick_dt) {
+    const std::string fn = "srbm_controller_advance";
+    if (!h) return fail(fn + ": bad arguments (NULL handle)");
+    return controller_advance(fn, h, nullptr, first_tick, ticks, ticks_per_update, tick_dt, 0);
+}
+int srbm_gait_controller_advance(srbm_gait* g, int first_tick, int ticks, int ticks_per_update, double tick_dt, int gait_opt_freq) {
+    const std::string fn = "srbm_gait_controller_advance";
+    if (!g) return fail(fn + ": bad arguments (NULL handle)");
+    if (gait_opt_freq <= 0) return fail(fn + ": gait_opt_freq > 0 is required");
+    return controller_advance(fn, g->h, g, first_tick, ticks, ticks_per_update, tick_dt, gait_opt_freq);
 }
 // ---- the tick log (include/srbm_rti.h; the record is written by srbm_k_wb_plant_step<true>) ----
 int srbm_tick_log_record_doubles(void) { return SRBM_TICK_LOG_DOUBLES; }

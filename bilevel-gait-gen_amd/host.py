@@ -244,6 +244,10 @@ int srbm_wb_plant_set_contact_state(srbm_batch*, double*)
 int srbm_wb_ground_dynamics(srbm_batch*, double*, double*, double*, double*, double*, double*, int*)
 int srbm_wb_ground_dynamics_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_wb_ground_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, dev*, dev*)
+int srbm_controller_set_contact_feedback(srbm_batch*, int)
+int srbm_controller_get_contact_feedback(srbm_batch*, double*)
+int srbm_controller_contact_feedback_dev(srbm_batch*, dev*, dev*)
+int srbm_gait_controller_advance(srbm_gait*, int, int, int, double, int)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

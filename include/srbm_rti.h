@@ -667,8 +667,9 @@ int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, 
  * cs is carried from sub-step to sub-step and, in the batch, from tick to tick.  A sub-step whose factorisation meets a pivot that is not finite or not
  * positive takes a = 0 and reports (a, F) = 0 (flags bit 3 of the tick); its contact state is what the law left.
  * What it is NOT: compliant, not rigid (a foot that carries N sinks by N / k_n); no impact law; no LCP; no terrain but one horizontal plane per
- * instance; and the controller keeps believing its plan (no AdjustForCurrentContacts): tick log fields 43..46 against field 63 show where the plan and
- * the ground disagree.
+ * instance.  The plan is told of the ground's contacts only with srbm_controller_set_contact_feedback on (below: MPC::AdjustForCurrentContacts before
+ * every MPC update); off, the default, the controller keeps believing its plan.  Tick log fields 43..46 against field 63 show where the plan and the
+ * ground disagree.
  *
  * srbm_wb_plant_set_ground: ground[batch][8]; NULL removes the ground, kind 1 is then the held-feet plant again.  Kind 0 ignores a ground.  Refused,
  * naming the instance and the field, the batch untouched: a field that is not finite (z0 may be -inf) or outside its range; a reserved field != 0.
@@ -691,6 +692,40 @@ int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double
  * srbm_controller_advance launches this kernel on the batch's (q, v, cs) when the kind is 1 and a ground is set; nothing else in it changes. */
 int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, double* cs_dev, const double* control_dev,
                             const int* status_dev, double* sol_dev);
+
+/* ---- the MPC update of the rollout in full: MPCController::MPCUpdate (controllers/mpc_controller.cpp:299-346) ----
+ * Step 3 of srbm_controller_advance is MPC::GetRealTimeUpdate alone.  The reference's update does two more things, both off by default here.
+ *
+ * Contact feedback (replaces mpc_controller.cpp:322, mpc_.AdjustForCurrentContacts(time, contact) -> mpc/mpc.cpp:1195-1203): with the setting on,
+ * every update tick k of srbm_controller_advance runs, between the control tick and the plant step, the rule of srbm_adjust_for_current_contacts on
+ * the time array of the tick (t_k) and the batch's contact state cs: foot i counts as measured in contact iff cs[3 i] != 0.  At that point cs is the
+ * ground's state after tick k - 1, the contact the reference's simulator measures at t_k and hands to ComputeControlAction
+ * (simulation/simulation_robot.cpp:144-156).  A foot on the ground whose plan says swing and whose planned touch-down is less than 70 ms away has
+ * that touch-down moved to t_k; the error bits are those of srbm_adjust_for_current_contacts (64 where the reference throws).  The control tick of
+ * tick k has read the old knot tables, the plant step reads none: the new schedule is in force from the update on.  One launch on the batch's
+ * stream, no copy, no synchronisation.  The tick log and the step log keep their layouts (the measured flags at t_k are field 63 bits 0..3 of the
+ * record of tick k - 1).
+ * srbm_controller_set_contact_feedback: on = 0 (the default) | 1.  With it on, srbm_controller_advance and srbm_gait_controller_advance are refused,
+ * naming the setting, with the batch untouched, unless the plant is of kind 1 with a ground set: without a ground nothing measures a contact.
+ * The feedback record fb[batch][8]: per foot {number of touch-downs moved, t of the last move (-1 if none)}; srbm_wb_plant_set_state resets it,
+ * srbm_controller_get_contact_feedback reads it (after the work queued so far).  srbm_batch_clone carries the setting and the record.
+ * srbm_controller_contact_feedback_dev: the kernel alone on the caller's device arrays time_dev[batch], cs_dev[batch][12], for tests and host-driven
+ * chains; it counts in fb the same way.  Refused before srbm_wb_plant_set_state (which allocates fb). */
+int srbm_controller_set_contact_feedback(srbm_batch* h, int on);
+int srbm_controller_get_contact_feedback(srbm_batch* h, double* fb);
+int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, const double* cs_dev);
+/* The gait step (replaces mpc_controller.cpp:324-346, the branch on the run number): srbm_controller_advance on the batch of `g` -- the same
+ * loop, the same refusals, the same tick and plant launches, contact feedback before the update when it is on -- with the update after tick k,
+ * run r = k / ticks_per_update (r >= 1), branched as srbm_gait_rti_advance branches on r, F = gait_opt_freq:
+ *     r % F == 0          GaitOptimizer::LineSearch for the instances whose gradient is ready, the plain update (zero-step candidates) for the others
+ *     (r + 1) % F == 0    an RTI taken to the gap criterion whatever the batch's step rule says, then gradient and LP; ready := valid && lp_status == 0
+ *     otherwise           the plain update; ready := 0
+ * on the state, time and ee of the tick, as srbm_get_real_time_update_dev takes them.  The ready flags live in `g` and r follows from k: a rollout
+ * split into several calls is the same rollout.  With a step log enabled every update writes one record: plain runs as srbm_controller_advance
+ * writes them, gradient and line-search runs with fields 58..63 as srbm_gait_closed_loop_advance writes them.  With F beyond the last run number the
+ * entry is bitwise srbm_controller_advance.  Refused in addition: a NULL handle, gait_opt_freq <= 0.  The caller's own srbm_gait_compute_gradient /
+ * _sensitivity after a rollout still refuse a last solve that ended by the step rule. */
+int srbm_gait_controller_advance(srbm_gait* g, int first_tick, int ticks, int ticks_per_update, double tick_dt, int gait_opt_freq);
 
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */

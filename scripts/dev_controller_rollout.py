@@ -10,6 +10,10 @@ medians and spreads.
   (e) ground     (d) with a compliant ground set (srbm_wb_plant_set_ground: k_n 2e4, d_n 100, mu 0.7, k_t 1e4, d_t 50, the plane 3 mm above each
                  instance's lowest foot at the start), logged, S = 1 and 4; beside (d) this is what the ground costs.  And its step kernel alone
                  (srbm_wb_ground_step_dev, S = 1 and 4), as (c)
+  (f) feedback   (e) at S = 4 with contact feedback on (srbm_controller_set_contact_feedback: one small launch per MPC update); beside (e) this is
+                 what the feedback costs -- per update: the difference times ticks_per_update
+  (g) gait       (e) at S = 4 through srbm_gait_controller_advance with gait_opt_freq 5, feedback off, 250 ticks so that the updates are three plain
+                 ones, one with gradient and LP (run 4) and one line search (run 5); ms per tick over those 250 ticks
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -32,6 +36,7 @@ F = dict(TICK_LOG_FIELDS, **TORQUE_PLANT_LOG_FIELDS)
 G = dict(TICK_LOG_FIELDS, **GROUND_PLANT_LOG_FIELDS)
 B, TICKS, TPU, DT, LIMIT_S = 256, 200, 50, 1e-3, 60.0
 RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+GAIT_TICKS, GAIT_FREQ = 250, 5
 
 
 def main():
@@ -44,7 +49,8 @@ def main():
     q_init = np.tile(np.array(cfg['init_config'], float), (B, 1))
     q0, v0, _, st = base.clone().get_targets_from_traj(0.0, q_init)          # the plant starts on the targets of tick 0
     res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': [], 'torque_s1_logged': [], 'torque_s4_logged': [], 'fd_step_s1': [], 'fd_step_s4': [],
-           'ground_s1_logged': [], 'ground_s4_logged': [], 'ground_step_s1': [], 'ground_step_s4': []}
+           'ground_s1_logged': [], 'ground_s4_logged': [], 'ground_step_s1': [], 'ground_step_s4': [], 'ground_s4_feedback_logged': [],
+           'ground_s4_gait_f5_logged': []}
     ground = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
@@ -118,6 +124,34 @@ def main():
                               feet_in_contact_mean=float(word['in_contact'].sum(axis=-1).mean()), slipping_feet_mean=float(word['slipping'].sum(axis=-1).mean()),
                               feet_off_the_plan_mean=float(word['plan_differs'].sum(axis=-1).mean()),
                               median_accel_mismatch=float(np.median(log[:, :, G['accel_mismatch']])))
+        # (f) ... with contact feedback on
+        g, R = fresh(TICKS + 3)
+        R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
+        R.set_ground(ground)
+        R.set_contact_feedback(True)
+        signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+        R.advance(0, 3, TPU, DT)
+        signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+        res['ground_s4_feedback_logged'].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+        fb = R.contact_feedback()
+        info['ground_s4_feedback_logged'] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), touch_downs_moved=int(fb[:, :, 0].sum()),
+                                                 instances_with_a_move=int((fb[:, :, 0].sum(axis=1) > 0).sum()),
+                                                 error_bits=int(np.bitwise_or.reduce(g.status_accumulated()[:, 0])))
+        # (g) ... and with the gait step in the updates
+        g, R = fresh(GAIT_TICKS + 3)
+        R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
+        R.set_ground(ground)
+        gait = host.BatchGaitOptimizer(g)
+        g.step_log_enable(GAIT_TICKS // TPU + 1)
+        signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+        R.advance(0, 3, TPU, DT, gait=gait, gait_opt_freq=GAIT_FREQ)
+        signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+        res['ground_s4_gait_f5_logged'].append(timed(g, lambda: R.advance(3, GAIT_TICKS, TPU, DT, gait=gait, gait_opt_freq=GAIT_FREQ)) * TICKS / GAIT_TICKS)
+        steps = g.step_log()
+        info['ground_s4_gait_f5_logged'] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), ticks=GAIT_TICKS, run_kinds=[int(x) for x in steps[:, 0, 58]],
+                                                ready_after_the_gradient_run=int(steps[:, :, 59].max(axis=0).sum()),
+                                                searched_in_the_line_search=int((steps[:, :, 58] == 2).sum()))
+        gait.close()
         # (b) the same loop from the host, on torch's buffers, on the batch's stream
         g, R = fresh()
         T = ControlTick(g)
