@@ -2199,6 +2199,11 @@ int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
     const WbBuf w = wb_buf(h);
     return fetch(h, {{q, w.q, sizeof(double) * 19 * (size_t)h->batch}, {v, w.v, sizeof(double) * 18 * (size_t)h->batch}});
 }
+// the refusal of a tick the step entries cannot run
+static int check_tick(const char* fn, int tick, double tick_dt) {
+    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(std::string(fn) + ": tick >= 0 and a finite tick_dt > 0 are required");
+    return 0;
+}
 // the plant step of tick `tick` on the batch's stream; lg: the record of the tick, nullptr: the unlogged kernel
 static int launch_wb_plant(srbm_batch* h, int tick, double tick_dt, double* q, double* v, const double* qp_sol, const int* status, double* time_next,
                            const SrbmTickLogArgs* lg) {
@@ -2211,8 +2216,7 @@ static int launch_wb_plant(srbm_batch* h, int tick, double tick_dt, double* q, d
 }
 int srbm_wb_plant_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* qp_sol_dev, const int* status_dev) {
     if (!h || !q_dev || !v_dev || !qp_sol_dev || !status_dev) return fail("srbm_wb_plant_step_dev: bad arguments");
-    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_plant_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
-    if (use_batch(h)) return -1;
+    if (check_tick("srbm_wb_plant_step_dev", tick, tick_dt) || use_batch(h)) return -1;
     return launch_wb_plant(h, tick, tick_dt, q_dev, v_dev, qp_sol_dev, status_dev, nullptr, nullptr);
 }
 // ---- the torque-driven plant (srbm_wb_fd.hiph) ----
@@ -2284,6 +2288,24 @@ static int fd_usable(srbm_batch* h, const char* fn) {
         return fail(std::string(fn) + ": the whole-body model has not been set (srbm_set_wbc_model), and the plant has no bodies of its own (srbm_wb_plant_set_bodies_each)");
     return 0;
 }
+// the torque-driven plant step of tick `tick` on the batch's stream: on the ground with the contact state cs, with the feet of `contact` held where
+// cs is nullptr; contact (on a ground: the plan's) and qp_sol are the tick's, for the record; lg: the record of the tick, nullptr: the unlogged kernel
+static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
+                            const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
+    const double* push = h->push_set ? h->d_push : nullptr;
+    int stride = 0;
+    const SrbmBody* bodies = fd_bodies(h, &stride);
+    const SrbmFdArgs fa{bodies, stride, h->d_fd_act, h->fd_substeps, control, contact, qp_sol, sol_out};
+    const SrbmGroundArgs ga{h->d_ground, cs};
+    const SrbmTickLogArgs l = lg ? *lg : SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0};
+    const dim3 grid(h->batch), block(WBC_THREADS);
+    if (cs && lg) hipLaunchKernelGGL((srbm_k_wb_ground_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, l);
+    else if (cs) hipLaunchKernelGGL((srbm_k_wb_ground_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, l);
+    else if (lg) hipLaunchKernelGGL((srbm_k_wb_fd_step<true>), grid, block, 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, l);
+    else hipLaunchKernelGGL((srbm_k_wb_fd_step<false>), grid, block, 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, l);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 int srbm_wb_forward_dynamics_dev(srbm_batch* h, const double* q_dev, const double* v_dev, const double* tau_dev, const int* contact_dev, double* sol_dev, int* status_dev) {
     if (!h || !q_dev || !v_dev || !tau_dev || !contact_dev || !sol_dev || !status_dev) return fail("srbm_wb_forward_dynamics: bad arguments");
     if (fd_usable(h, "srbm_wb_forward_dynamics") || use_batch(h)) return -1;
@@ -2316,27 +2338,13 @@ int srbm_wb_forward_dynamics(srbm_batch* h, const double* q, const double* v, co
     if (status) memcpy(status, c.host(ost), ost.bytes());
     return 0;
 }
-// the torque-driven plant step of tick `tick` on the batch's stream; qp_sol: the tick's, for the record (lg != nullptr)
-static int launch_wb_fd(srbm_batch* h, int tick, double tick_dt, double* q, double* v, const double* control, const int* contact, const int* status,
-                        const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
-    const double* push = h->push_set ? h->d_push : nullptr;
-    int stride = 0;
-    const SrbmBody* bodies = fd_bodies(h, &stride);
-    const SrbmFdArgs fa{bodies, stride, h->d_fd_act, h->fd_substeps, control, contact, qp_sol, sol_out};
-    if (lg) hipLaunchKernelGGL((srbm_k_wb_fd_step<true>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, *lg);
-    else hipLaunchKernelGGL((srbm_k_wb_fd_step<false>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next,
-                            SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0});
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, const double* control_dev, const int* contact_dev,
                         const int* status_dev, double* sol_dev) {
     if (!h || !q_dev || !v_dev || !control_dev || !contact_dev || !status_dev) return fail("srbm_wb_fd_step_dev: bad arguments");
-    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_fd_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
-    if (fd_usable(h, "srbm_wb_fd_step_dev")) return -1;
+    if (check_tick("srbm_wb_fd_step_dev", tick, tick_dt) || fd_usable(h, "srbm_wb_fd_step_dev")) return -1;
     if (!h->d_fd_act) return fail(std::string("srbm_wb_fd_step_dev: ") + FD_NO_ACTUATORS);
     if (use_batch(h)) return -1;
-    return launch_wb_fd(h, tick, tick_dt, q_dev, v_dev, control_dev, contact_dev, status_dev, nullptr, sol_dev, nullptr, nullptr);
+    return launch_wb_torque(h, tick, tick_dt, q_dev, v_dev, nullptr, control_dev, contact_dev, status_dev, nullptr, sol_dev, nullptr, nullptr);
 }
 // ---- the ground of the torque-driven plant (srbm_wb_ground.hiph) ----
 static const char* const WB_NO_STATE = "the whole-body plant state has not been set (srbm_wb_plant_set_state)";
@@ -2432,28 +2440,13 @@ int srbm_wb_ground_dynamics(srbm_batch* h, const double* q, const double* v, con
     if (status) memcpy(status, c.host(ost), ost.bytes());
     return 0;
 }
-// the ground step of tick `tick` on the batch's stream; contact (the plan's) and qp_sol: the tick's, for the record (lg != nullptr)
-static int launch_wb_ground(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
-                            const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
-    const double* push = h->push_set ? h->d_push : nullptr;
-    int stride = 0;
-    const SrbmBody* bodies = fd_bodies(h, &stride);
-    const SrbmFdArgs fa{bodies, stride, h->d_fd_act, h->fd_substeps, control, contact, qp_sol, sol_out};
-    const SrbmGroundArgs ga{h->d_ground, cs};
-    if (lg) hipLaunchKernelGGL((srbm_k_wb_ground_step<true>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, *lg);
-    else hipLaunchKernelGGL((srbm_k_wb_ground_step<false>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next,
-                            SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0});
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, double* cs_dev, const double* control_dev, const int* status_dev,
                             double* sol_dev) {
     if (!h || !q_dev || !v_dev || !cs_dev || !control_dev || !status_dev) return fail("srbm_wb_ground_step_dev: bad arguments");
-    if (tick < 0 || !std::isfinite(tick_dt) || tick_dt <= 0.0) return fail("srbm_wb_ground_step_dev: tick >= 0 and a finite tick_dt > 0 are required");
-    if (ground_usable(h, "srbm_wb_ground_step_dev")) return -1;
+    if (check_tick("srbm_wb_ground_step_dev", tick, tick_dt) || ground_usable(h, "srbm_wb_ground_step_dev")) return -1;
     if (!h->d_fd_act) return fail(std::string("srbm_wb_ground_step_dev: ") + FD_NO_ACTUATORS);
     if (use_batch(h)) return -1;
-    return launch_wb_ground(h, tick, tick_dt, q_dev, v_dev, cs_dev, control_dev, nullptr, status_dev, nullptr, sol_dev, nullptr, nullptr);
+    return launch_wb_torque(h, tick, tick_dt, q_dev, v_dev, cs_dev, control_dev, nullptr, status_dev, nullptr, sol_dev, nullptr, nullptr);
 }
 // ---- contact feedback from the ground (srbm_contact_feedback.hiph) ----
 static int launch_contact_feedback(srbm_batch* h, const double* time, const double* cs) {
@@ -2541,10 +2534,9 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
         // mpc_controller.cpp:322: the contacts measured at t_k -- the ground's state after tick k - 1 -- re-time the plan the update starts from
         if (update && h->contact_fb && launch_contact_feedback(h, time, h->d_cs)) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
-        if (h->fd_kind == 1 && h->d_ground) {
-            if (launch_wb_ground(h, k, tick_dt, w.q, w.v, h->d_cs, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
-        } else if (h->fd_kind == 1) {
-            if (launch_wb_fd(h, k, tick_dt, w.q, w.v, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
+        if (h->fd_kind == 1) {
+            if (launch_wb_torque(h, k, tick_dt, w.q, w.v, h->d_ground ? h->d_cs : nullptr, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B,
+                                 h->d_tlog ? &lg : nullptr)) return -1;
         } else if (launch_wb_plant(h, k, tick_dt, w.q, w.v, w.sol, w.status, w.time + ((k + 1) & 1) * B, h->d_tlog ? &lg : nullptr)) return -1;
         if (h->d_tlog) h->tlog_used++;
         // the hand-off of mpc_controller.cpp:142-156: the state and foot positions of THIS tick to the solve, the new trajectories in force from tick k + 1
