@@ -418,6 +418,17 @@ int srbm_debug_get_spline_step(srbm_batch* h, int inst, double* u_prev, double* 
                      {cols4 + 3 * SRBM_NUMAX, W(offsetof(SrbmWork, col_local)), ni}, {fix, W(offsetof(SrbmWork, fix_mask)), ni}});
 }
 
+// diagnostic: what the condensing kernel left in the work record of instance `inst` at its last solve, at the capacities of this build -- H packed
+// lower [NUMAX (NUMAX + 1) / 2], g [NUMAX], the compact dense state rows Sig [2 (NMAX - 3)][NUMAX], sig0 [2 (NMAX - 3)] -- with the instance's
+// n_u and error bits (tests/test_gpu_condense.py, scripts/dev_bitwise_ab.py)
+int srbm_debug_get_condensed(srbm_batch* h, int inst, double* H, double* g, double* Sig, double* sig0, int* nu, int* err) {
+    if (!h || inst < 0 || inst >= h->batch || !H || !g || !Sig || !sig0 || !nu || !err) return fail("bad arguments");
+    auto W = [&](size_t offset) { return work_field(h, inst, offset); };
+    return fetch(h, {{H, W(offsetof(SrbmWork, H)), sizeof(SrbmWork::H)}, {g, W(offsetof(SrbmWork, g)), sizeof(SrbmWork::g)},
+                     {Sig, W(offsetof(SrbmWork, Sig)), sizeof(SrbmWork::Sig)}, {sig0, W(offsetof(SrbmWork, sig0)), sizeof(SrbmWork::sig0)},
+                     {nu, W(offsetof(SrbmWork, nu)), sizeof(int)}, {err, &h->insts[inst].err, sizeof(int)}});
+}
+
 // device buffers + kernel attributes of a batch whose host parameters (h->hp, batch, device) are set; on failure everything
 // allocated so far is released by the caller through free_batch()
 static void free_batch(srbm_batch* h) {

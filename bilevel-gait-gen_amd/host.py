@@ -288,7 +288,8 @@ int srbm_debug_h_stage(int, int, double*, double*, int, int, int, int*)
 int srbm_debug_get_trace(srbm_batch*, int, double*)
 int srbm_debug_get_spline_step(srbm_batch*, int, double*, double*, int*, int*)
 int srbm_debug_get_instance_iters(srbm_batch*, double*)
-int srbm_debug_get_launch_info(srbm_batch*, int*)''')
+int srbm_debug_get_launch_info(srbm_batch*, int*)
+int srbm_debug_get_condensed(srbm_batch*, int, double*, double*, double*, double*, int*, int*)''')
 
 
 def build(force=False):
@@ -1063,3 +1064,20 @@ def dense_row_placement(N, nu, wc, large=False):
     if L.srbm_debug_dense_row_placement(int(N), int(nu), int(wc), out) != 0:
         raise ValueError(L.srbm_last_error().decode())
     return out[0], out[1], bool(out[2])
+
+
+def condensed(mpc, inst):
+    """srbm_debug_get_condensed: what the condensing kernel left in the work record of instance `inst` at its last solve, trimmed to the
+    instance's sizes -- H (n_u x n_u, both triangles filled from the packed lower one), g [n_u], the compact dense state rows Sig
+    [2 (N - 3)][n_u] (row 2 (k - 4) + c: position c of node k on the force variables of coordinate c), sig0 [2 (N - 3)], n_u, the error bits;
+    `packed` is the packed lower triangle as the kernel wrote it (what scripts/dev_bitwise_ab.py compares byte for byte)"""
+    NU, rows_cap, rows = mpc.NUMAX, 2 * (mpc.L.capacity['N'] - 3), 2 * (mpc.N - 3)
+    Hp = np.zeros(NU * (NU + 1) // 2); g = np.zeros(NU); Sig = np.zeros((rows_cap, NU)); sig0 = np.zeros(rows_cap)
+    nu = np.zeros(1, np.int32); err = np.zeros(1, np.int32)
+    read = mpc.L.srbm_debug_get_condensed
+    mpc._chk(read(mpc.h, int(inst), _d(Hp), _d(g), _d(Sig), _d(sig0), _i(nu), _i(err)))
+    n = int(nu[0])
+    H = np.zeros((n, n))
+    H[np.tril_indices(n)] = Hp[:n * (n + 1) // 2]
+    H = H + np.tril(H, -1).T
+    return dict(H=H, g=g[:n].copy(), Sig=Sig[:rows, :n].copy(), sig0=sig0[:rows].copy(), nu=n, err=int(err[0]), packed=Hp[:n * (n + 1) // 2].copy())

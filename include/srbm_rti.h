@@ -761,6 +761,11 @@ int srbm_get_knots(srbm_batch* h, int inst, double* times, int* kinds, int* nk, 
 /* Dense expansion of the structured QP of the LAST solve of one instance into the reference's layout
  * (rows/cols as SURVEY.md Appendix A): A[m][n], b[m], P[n][n], q[n].  Debug / parity-test aid. */
 int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* P, double* q);
+/* What the condensing left in the work record of one instance at its LAST solve, at the capacities of the loaded build (srbm_get_capacity: N_max,
+ * n_u_max): H[n_u_max (n_u_max + 1) / 2] packed lower by rows, g[n_u_max], the compact dense state rows Sig[2 (N_max - 3)][n_u_max] (row 2 (k - 4) + c
+ * = position c of node k on the force variables of coordinate c over the four feet), sig0[2 (N_max - 3)], the instance's n_u and its error bits.
+ * Debug / parity-test aid like srbm_export_qp. */
+int srbm_debug_get_condensed(srbm_batch* h, int inst, double* H, double* g, double* Sig, double* sig0, int* nu, int* err);
 /* result records for collection across GPUs (one RCCL all-gather in bench.py): out_dev[batch][ld] on
  * the handle's stream.  Layout of one record (doubles), NX = 12 (N+1) + n_u_max, NM = 12 (N+1) + 6 * samples_max + 16 (N-3) + 16 with the capacities of the loaded build
  * (srbm_get_capacity: 160 / 120 in the standard build, 240 / 200 in the LARGE one):

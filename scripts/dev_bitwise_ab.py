@@ -1,7 +1,8 @@
 """Bitwise A/B of the RTI step between two library builds: python scripts/dev_bitwise_ab.py <parent's libsrbm_rti.so> <branch's libsrbm_rti.so>
 Each library runs in its own process (SRBM_RTI_LIB).  8 seeded Config-B instances and 4 Config-D instances (N = 50: the *_long body, 3 rows per
 thread): cold start in the bench's solver mode (0, 0.1), then 6 fused steps in two launches of 3 -- long enough for a repeated lower-start attempt and for
-both n_u values of the schedule.  After each launch: the packed result records, the sizes, the flags of the solve; at the end the sticky accumulators,
+both n_u values of the schedule.  After each launch: the packed result records, the sizes, the flags of the solve, and what the condensing of the launch's last step left in every
+work record (packed H, g, the compact Sig rows, sig0, n_u, error bits: host.condensed); at the end the sticky accumulators,
 the solver counters and the per-instance iteration counts.  Prints what each build saw (n_u values, attempts tried / repeated) and exits 1 on any
 differing byte.  For a change of the kernels that is meant to leave every result alone (scripts/README.md, identity of two builds, when the
 instructions may differ)."""
@@ -26,6 +27,10 @@ if len(sys.argv) > 1 and sys.argv[1] == '--child':
             out['%s step %d: records' % (wl, k)] = g.pack_results()
             out['%s step %d: sizes' % (wl, k)] = g.sizes()
             out['%s step %d: flags' % (wl, k)] = g.solve_flags()
+            cd = [host.condensed(g, b) for b in range(B)]          # what the condensing of the launch's last step left in the work records
+            for key in ('packed', 'g', 'Sig', 'sig0'):
+                out['%s step %d: condensed %s' % (wl, k, key)] = np.concatenate([c[key].ravel() for c in cd])
+            out['%s step %d: condensed nu, err' % (wl, k)] = np.array([[c['nu'], c['err']] for c in cd])
         for key, v in snapshot(g, False).items():
             out['%s end: %s' % (wl, key)] = v
         c = g.solver_counters()
