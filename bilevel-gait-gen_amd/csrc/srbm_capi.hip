@@ -393,6 +393,16 @@ int srbm_debug_h_stage(int n, int count, const double* H_packed, double* out, in
     return run_dense_hook(srbm_k_debug_h_stage, count, K3_LDS_LAUNCH_BYTES, {}, {{out, dout, ob}, {map5, dmap, mb}}, n, dW, dout, guard, N, wc,
                           (int)(K3_LDS_LAUNCH_BYTES / sizeof(double)), dmap);
 }
+/* unit-test hook of the constant LDS base of the out-of-line device functions (SRBM_LDS_BASE, srbm_types.h), `count` workgroups: out4[count][4] <- the
+   LDS address of the dynamic LDS as the kernel has it, the address an out-of-line function uses, the constant, and 0x5eed if a value the
+   out-of-line function stored at double `slot` (< 64) of its dynamic LDS is read back by the kernel at the same slot of its own (0 otherwise) */
+int srbm_debug_lds_base(int count, int slot, int* out4) {
+    if (count <= 0 || slot < 0 || slot >= DBG_LDS_BASE_DOUBLES || !out4) return fail("bad arguments");
+    unsigned* dout = nullptr;
+    DevTemps tmp;
+    HIPCHK(tmp.alloc(&dout, sizeof(unsigned) * 4 * count));
+    return run_dense_hook(srbm_k_debug_lds_base, count, DBG_LDS_BASE_DOUBLES * sizeof(double), {}, {{out4, dout, sizeof(unsigned) * 4 * count}}, slot, dout);
+}
 /* host only: where the IPM of this library puts the 2 (N - 3) compact dense state rows of width wc at n_u = nu (k3_sig_placement, the arithmetic of
    its LDS map): out3 = rows in the tail of the packed-matrix window, rows behind the LDS map, 1 if all are in LDS (0: read from L2) */
 int srbm_debug_dense_row_placement(int N, int nu, int wc, int* out3) {

@@ -22,6 +22,47 @@
 #define SRBM_LDS_ALIGN
 #endif
 extern __shared__ SRBM_LDS_ALIGN double srbm_lds[];
+/* ONLY KERNELS, AND CODE INLINED INTO THEM, MAY NAME THIS SYMBOL (standard and diagnostic build).  A device function that is not a kernel begins with
+   SRBM_LDS_OUT_OF_LINE() or SRBM_LDS_OUT_OF_LINE_LITERAL(), which declare a local pointer of the same name in its place; one that forgets the line, or
+   a helper inlined into it that names the global, still compiles -- what catches it is tests/test_code_object_lds.py (no GPU), which fails as soon as
+   the compiler's table below is back in the code object.
+
+   The LDS address of srbm_lds, as a constant.  A KERNEL that names srbm_lds gets the address at no cost.  A function that is not a kernel gets it from
+   a table in memory that the compiler keeps per kernel, llvm.amdgcn.dynlds.offset.table (a scalar load behind s_getpc, waited for with lgkmcnt(0), and
+   loaded again wherever the address is rematerialised -- 41 times in dn_factor_invert).  Every kernel of a build that reaches such a function has the
+   same static LDS in front of its dynamic LDS -- none, or the diagnostic build's clock -- so the table holds one value, said here: after the line above
+   the name srbm_lds means, in that function, a pointer made from the constant (the macros K3_M and DN_XPTR and a K3Smem made there follow), no function
+   that is not a kernel names the extern symbol, and the table is not emitted.
+   The constant is checked, not trusted: the test named above holds the static LDS (group_segment_fixed_size) of every kernel that reaches an
+   out-of-line LDS user to it in each built library, and srbm_debug_lds_base compares both addresses on the device.
+   The LARGE build keeps the symbol and the table (the two macros are empty there): without the table its Config E ran 1.2 - 1.9 % slower in either form
+   of the constant, with equal or fewer spills, and why was not found (docs/history.md); its matrix is not in LDS, and its look-ups are fewer. */
+#ifdef SRBM_PROFILE
+#define SRBM_LDS_BASE 16u
+#else
+#define SRBM_LDS_BASE 0u
+#endif
+#ifdef __HIPCC__
+typedef __attribute__((address_space(3))) double* SrbmLdsPtr;
+/* Two forms, chosen per function from the scratch of the kernels and the A/B of docs/history.md.  SRBM_LDS_OUT_OF_LINE() sends the value through an
+   empty asm into a scalar register, once per function: it is then what the table's load gave, but cannot be rematerialised by loading it again.
+   SRBM_LDS_OUT_OF_LINE_LITERAL() leaves the literal, which is folded into every LDS instruction.
+   -DSRBM_LDS_LITERAL: the literal everywhere, for that A/B. */
+template <bool LITERAL> __device__ __forceinline__ double* srbm_lds_out_of_line() {
+    unsigned base = SRBM_LDS_BASE;
+#ifndef SRBM_LDS_LITERAL
+    if (!LITERAL) asm volatile("" : "+s"(base));
+#endif
+    return (double*)(SrbmLdsPtr)(size_t)base;
+}
+#ifdef SRBM_LARGE
+#define SRBM_LDS_OUT_OF_LINE() ((void)0)
+#define SRBM_LDS_OUT_OF_LINE_LITERAL() ((void)0)
+#else
+#define SRBM_LDS_OUT_OF_LINE() double* const srbm_lds = srbm_lds_out_of_line<false>()
+#define SRBM_LDS_OUT_OF_LINE_LITERAL() double* const srbm_lds = srbm_lds_out_of_line<true>()
+#endif
+#endif
 
 #define SRBM_NEE 4
 /* Where the packed normal matrix of the IPM lives: LDS (standard build: one workgroup of 512 threads per CU) or the work record in global

@@ -285,6 +285,7 @@ int srbm_debug_sym_matvec(int, int, double*, double*, double*)
 int srbm_debug_hmatvec(int, int, double*, double*, double*)
 int srbm_debug_dense_row_placement(int, int, int, int*)
 int srbm_debug_h_stage(int, int, double*, double*, int, int, int, int*)
+int srbm_debug_lds_base(int, int, int*)
 int srbm_debug_get_trace(srbm_batch*, int, double*)
 int srbm_debug_get_spline_step(srbm_batch*, int, double*, double*, int*, int*)
 int srbm_debug_get_instance_iters(srbm_batch*, double*)
