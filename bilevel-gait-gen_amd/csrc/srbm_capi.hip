@@ -25,6 +25,7 @@
 #include "srbm_wb_ground.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_rollout_summary.hiph"
+#include "srbm_tick_summary.hiph"
 #include "srbm_batch.hiph"
 #include "srbm_dense_hooks.hiph"
 #include "../../include/srbm_rti.h"
@@ -106,6 +107,11 @@ struct srbm_batch {
     int* d_wb_int = nullptr;         // [WB_INTS][batch]
     double* d_tlog = nullptr;        // tick log [tlog_cap][batch][SRBM_TICK_LOG_DOUBLES], nullptr: logging off
     int tlog_cap = 0, tlog_used = 0; // slots allocated; the cursor
+    // tick summaries (srbm_tick_summary.hiph): the tick log folded per instance, nullptr: off
+    double* d_tsum = nullptr;        // [batch][SRBM_TICK_SUMMARY_DOUBLES]
+    double* d_tsum_ref = nullptr;    // the references [batch][SRBM_TICK_REF_DOUBLES]
+    SrbmTickCriteria tsum_crit{};    // the criteria, a kernel argument
+    std::vector<double> tsum_init;   // host image of the summaries after a reset
     // the torque-driven plant (srbm_wb_fd.hiph): the kind srbm_controller_advance launches, the actuators and the plant's own bodies
     int fd_kind = 0;                 // 0: the QP-acceleration plant, 1: the torque-driven plant (srbm_wb_plant_set_kind)
     int fd_substeps = 1;
@@ -452,6 +458,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_sum); (void)hipFree(h->d_sum_ref);
     (void)hipFree(h->d_tick_q); (void)hipFree(h->d_tick_rec);
     (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
+    (void)hipFree(h->d_tsum); (void)hipFree(h->d_tsum_ref);
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
@@ -2623,6 +2630,128 @@ int srbm_tick_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out
     if (bytes == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(out_dev, src, bytes, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+// ---- tick summaries (include/srbm_rti.h; csrc/srbm_tick_summary.hiph): the entries of the rollout summaries, on the tick log ----
+int srbm_tick_summary_doubles(void) { return SRBM_TICK_SUMMARY_DOUBLES; }
+static_assert(SRBM_TICK_CRITERIA_DOUBLES == SRBM_ROLLOUT_CRITERIA_DOUBLES, "rollout_check_criteria checks both sets: finite, entries 6 and 7 zero");
+static int tick_summary_enabled(const srbm_batch* h, const char* fn) {
+    if (!h) return fail(std::string(fn) + ": bad arguments");
+    if (!h->d_tsum) return fail(std::string(fn) + ": no tick summary is enabled on this batch (srbm_tick_summary_enable)");
+    return 0;
+}
+static int tick_slots_outside(const char* fn, int first_slot, int count, int slots, const char* what) {
+    if (first_slot < 0 || count < 0 || first_slot > slots || count > slots - first_slot)
+        return fail(std::string(fn) + ": slots [" + std::to_string(first_slot) + ", " + std::to_string((long long)first_slot + count) + ") are outside the " +
+                    std::to_string(slots) + what);
+    return 0;
+}
+int srbm_tick_summary_reset(srbm_batch* h) {
+    if (tick_summary_enabled(h, "srbm_tick_summary_reset")) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_tsum, h->tsum_init.data(), sizeof(double) * h->tsum_init.size(), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+int srbm_tick_summary_enable(srbm_batch* h, const double* criteria, const double* ref) {
+    if (!h) return fail("srbm_tick_summary_enable: bad arguments");
+    if (criteria) {
+        if (!ref) return fail("srbm_tick_summary_enable: criteria without references (ref[batch][6])");
+        if (rollout_check_criteria("srbm_tick_summary_enable", criteria)) return -1;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_tsum) HIPCHK(hipFree(h->d_tsum));
+    h->d_tsum = nullptr;
+    if (h->d_tsum_ref) HIPCHK(hipFree(h->d_tsum_ref));
+    h->d_tsum_ref = nullptr;
+    if (!criteria) return 0;
+    const size_t B = h->batch;
+    std::memcpy(h->tsum_crit.c, criteria, sizeof(h->tsum_crit.c));
+    h->tsum_init.resize(B * SRBM_TICK_SUMMARY_DOUBLES);
+    for (size_t b = 0; b < B; b++) srbm_tick_summary_init(h->tsum_init.data() + b * SRBM_TICK_SUMMARY_DOUBLES);
+    HIPCHK(hipMalloc(&h->d_tsum_ref, sizeof(double) * SRBM_TICK_REF_DOUBLES * B));
+    HIPCHK(hipMemcpy(h->d_tsum_ref, ref, sizeof(double) * SRBM_TICK_REF_DOUBLES * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&h->d_tsum, sizeof(double) * SRBM_TICK_SUMMARY_DOUBLES * B));
+    return srbm_tick_summary_reset(h);
+}
+// the fold kernel on log[slots][batch][64] of the batch's device: the range is checked by the callers
+static int tick_fold_launch(srbm_batch* h, const double* log, int first_slot, int count) {
+    if (count == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(srbm_k_tick_fold, dim3(h->batch), dim3(64), 0, h->stream, log, h->batch, first_slot, count, h->tsum_crit, h->d_tsum_ref, h->d_tsum);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_tick_summary_fold(srbm_batch* h, int first_slot, int count) {
+    if (!h) return fail("srbm_tick_summary_fold: bad arguments");
+    if (!h->d_tlog) return fail("srbm_tick_summary_fold: no tick log is enabled on this batch (srbm_tick_log_enable)");
+    if (tick_summary_enabled(h, "srbm_tick_summary_fold")) return -1;
+    if (tick_slots_outside("srbm_tick_summary_fold", first_slot, count, h->tlog_used, " ticks logged")) return -1;
+    return tick_fold_launch(h, h->d_tlog, first_slot, count);
+}
+int srbm_tick_summary_fold_dev(srbm_batch* h, const double* log_dev, int slots, int first_slot, int count) {
+    if (!h || !log_dev || slots < 0) return fail("srbm_tick_summary_fold_dev: bad arguments");
+    if (tick_summary_enabled(h, "srbm_tick_summary_fold_dev")) return -1;
+    if (tick_slots_outside("srbm_tick_summary_fold_dev", first_slot, count, slots, " slots of the log")) return -1;
+    return tick_fold_launch(h, log_dev, first_slot, count);
+}
+int srbm_tick_summary_get(srbm_batch* h, int first, int count, double* out) {
+    if (tick_summary_enabled(h, "srbm_tick_summary_get")) return -1;
+    if (!out) return fail("srbm_tick_summary_get: bad arguments");
+    if (first < 0 || count < 0 || first > h->batch || count > h->batch - first)
+        return fail("srbm_tick_summary_get: instances [" + std::to_string(first) + ", " + std::to_string((long long)first + count) + ") are outside the batch of " +
+                    std::to_string(h->batch));
+    if (count == 0) return 0;
+    return fetch(h, {{out, h->d_tsum + (size_t)first * SRBM_TICK_SUMMARY_DOUBLES, sizeof(double) * SRBM_TICK_SUMMARY_DOUBLES * count}});
+}
+int srbm_tick_summary_copy_dev(srbm_batch* h, double* out_dev) {
+    if (tick_summary_enabled(h, "srbm_tick_summary_copy_dev")) return -1;
+    if (!out_dev) return fail("srbm_tick_summary_copy_dev: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out_dev, h->d_tsum, sizeof(double) * SRBM_TICK_SUMMARY_DOUBLES * (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+int srbm_tick_study_dev(srbm_batch* h, const double* summaries_dev, int instances, double* study_dev) {
+    if (!h || !summaries_dev || !study_dev || instances < 0) return fail("srbm_tick_study_dev: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    hipLaunchKernelGGL(srbm_k_tick_study, dim3(1), dim3(64), 0, h->stream, summaries_dev, instances, study_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_tick_study(srbm_batch* h, double* study) {
+    if (tick_summary_enabled(h, "srbm_tick_study")) return -1;
+    if (!study) return fail("srbm_tick_study: bad arguments");
+    void* d = nullptr;
+    if (batch_scratch(h, sizeof(double) * SRBM_TICK_STUDY_DOUBLES, &d)) return -1;
+    if (srbm_tick_study_dev(h, h->d_tsum, h->batch, static_cast<double*>(d))) return -1;
+    return fetch(h, {{study, d, sizeof(double) * SRBM_TICK_STUDY_DOUBLES}});
+}
+int srbm_tick_summary_allgather_dev(srbm_batch* h, ncclComm_t comm, double* out_dev) {
+    if (tick_summary_enabled(h, "srbm_tick_summary_allgather_dev")) return -1;
+    const size_t count = (size_t)h->batch * SRBM_TICK_SUMMARY_DOUBLES;
+    double* mine = nullptr;
+    if (allgather_slot("srbm_tick_summary_allgather_dev", h, comm, out_dev, count, &mine)) return -1;
+    if (srbm_tick_summary_copy_dev(h, mine)) return -1;
+    return allgather_run(h, comm, mine, out_dev, count);
+}
+// the same fold and the same reduction on the host: no GPU, no batch
+int srbm_tick_fold_host(const double* log, int slots, int batch, int first_slot, int count, const double* criteria, const double* ref, double* summaries) {
+    if (!log || !criteria || !ref || !summaries || slots < 0 || batch < 1) return fail("srbm_tick_fold_host: bad arguments");
+    if (rollout_check_criteria("srbm_tick_fold_host", criteria)) return -1;
+    if (tick_slots_outside("srbm_tick_fold_host", first_slot, count, slots, " slots of the log")) return -1;
+    for (int b = 0; b < batch; b++)
+        for (int s = first_slot; s < first_slot + count; s++)
+            srbm_tick_fold_record(summaries + (size_t)b * SRBM_TICK_SUMMARY_DOUBLES, log + ((size_t)s * batch + b) * SRBM_TICK_LOG_DOUBLES, criteria,
+                                  ref + (size_t)b * SRBM_TICK_REF_DOUBLES);
+    return 0;
+}
+int srbm_tick_study_host(const double* summaries, int instances, double* study) {
+    if (!summaries || !study || instances < 0) return fail("srbm_tick_study_host: bad arguments");
+    double U[SRBM_TICK_STUDY_DOUBLES];
+    srbm_tick_study_init(U);
+    for (int i = 0; i < instances; i++) srbm_tick_study_add(U, summaries + (size_t)i * SRBM_TICK_SUMMARY_DOUBLES);
+    std::memcpy(study, U, sizeof(U));
     return 0;
 }
 

@@ -232,6 +232,17 @@ int srbm_tick_log_reset(srbm_batch*)
 int srbm_tick_log_count(srbm_batch*, int*)
 int srbm_tick_log_get(srbm_batch*, int, int, double*)
 int srbm_tick_log_copy_dev(srbm_batch*, int, int, dev*)
+int srbm_tick_summary_doubles()
+int srbm_tick_summary_enable(srbm_batch*, double*, double*)
+int srbm_tick_summary_reset(srbm_batch*)
+int srbm_tick_summary_fold(srbm_batch*, int, int)
+int srbm_tick_summary_fold_dev(srbm_batch*, dev*, int, int, int)
+int srbm_tick_summary_get(srbm_batch*, int, int, double*)
+int srbm_tick_summary_copy_dev(srbm_batch*, dev*)
+int srbm_tick_study(srbm_batch*, double*)
+int srbm_tick_study_dev(srbm_batch*, dev*, int, dev*)
+int srbm_tick_fold_host(double*, int, int, int, int, double*, double*, double*)
+int srbm_tick_study_host(double*, int, double*)
 int srbm_wb_plant_set_kind(srbm_batch*, int)
 int srbm_wb_plant_set_actuators(srbm_batch*, double*, double*, double*, int)
 int srbm_wb_plant_set_bodies_each(srbm_batch*, double*, double*, double*)
@@ -266,6 +277,7 @@ int srbm_pack_results_dev(srbm_batch*, dev*, int)
 int srbm_pack_results(srbm_batch*, double*, int)
 int srbm_allgather_results(srbm_batch*, ncclComm_t, dev*)
 int srbm_rollout_allgather_dev(srbm_batch*, ncclComm_t, dev*)
+int srbm_tick_summary_allgather_dev(srbm_batch*, ncclComm_t, dev*)
 int srbm_rccl_get_unique_id(void*)
 int srbm_rccl_comm_init_rank(srbm_batch*, int, int, void*, ncclComm_t*)
 int srbm_rccl_comm_destroy(ncclComm_t)

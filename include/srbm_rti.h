@@ -595,6 +595,115 @@ int srbm_tick_log_count(srbm_batch* h, int* ticks_logged);
 int srbm_tick_log_get(srbm_batch* h, int first_slot, int count, double* out);
 int srbm_tick_log_copy_dev(srbm_batch* h, int first_slot, int count, double* out_dev);
 
+/* ---- tick summaries: the tick log folded into one outcome record per instance, on the device ----
+ * The tick-level counterpart of the rollout summaries above, which fold the step log (in a whole-controller rollout: one record per MPC update).
+ * What only the tick log holds -- the torques, a held foot that pulls, clamped joints, slipping feet, the plan against the ground -- without copying
+ * 512 bytes per tick and instance to the host.  The fold is INCREMENTAL in the same way: log a chunk of ticks, srbm_tick_summary_fold,
+ * srbm_tick_log_reset, repeat; a rollout of any length needs a tick log of one chunk, and the summaries are bit for bit independent of the chunking
+ * (every sum is accumulated in slot order).  The entries only read the log: no result changes.
+ *
+ * criteria[8], one set for the batch; ref[batch][6] = {p_ref[3], v_ref[3]} per instance, v_ref a linear velocity of the base.  R is a tick record
+ * (the layout above).  Deviations are squared and the tilt is measured as u = 2 (qx qx + qy qy) = 1 - cos(tilt), qx = R[9], qy = R[10]: the fold
+ * uses no division, square root or transcendental.
+ *     0  z_min        fallen if p_z < z_min, p_z = R[8]
+ *     1  tilt_max     fallen if u > tilt_max
+ *     2  r2_settle    in band needs d2 = dx dx + dy dy <= r2_settle, dx = R[6] - ref_x, dy = R[7] - ref_y
+ *     3  dz_settle    in band needs |p_z - ref_z| <= dz_settle
+ *     4  tilt_settle  in band needs u <= tilt_settle
+ *     5  v2_settle    in band needs |R[13..15] - v_ref|^2 <= v2_settle
+ *     6, 7            reserved, must be 0
+ * A record is in band when all four conditions hold.  A comparison with a NaN is false: a NaN never becomes a maximum or a minimum.
+ *
+ * One summary T, SRBM_TICK_SUMMARY_DOUBLES doubles, integers stored as doubles.  k is the 0-based ordinal of a record among those folded since the
+ * last reset.  After a reset: counts and sums 0, every maximum -inf, every minimum +inf, every ordinal and every carry -1.  Where two records tie,
+ * the first keeps the ordinal.  A field read as a set of bits (R[5], R[63] - 4096) is truncated to an integer; one that holds no set of bits
+ * (negative, 2^53 or more, NaN) has no bit set.
+ *     0         records folded
+ *     1, 2      tick index R[0] of the first and of the last record
+ *     3, 4      time R[1] of the first and of the last record
+ *     5, 6      count of targets status R[2] != 0; ordinal of the first such record
+ *     7, 8      count of QP status R[3] > 1 (the tick returned a zero control action); ordinal of the first such record
+ *     9, 10     sum and max of the QP iterations R[4]
+ *     11, 12    count of records with bit 0 of the flags R[5] (the push was applied); ordinal of the LAST such record
+ *     13..15    count of records with flags bit 1 (an MPC update followed), bit 2 (the plant coasted), bit 3 (a factorisation broke down)
+ *     31        count of records with a NaN among R[6..62]: such a record is counted here and in 0..15, and takes no part in 16..30 and 32..61
+ *     16, 17    min and max of p_z
+ *     18, 19    max d2 and the ordinal of its first occurrence
+ *     20, 21    max u and its ordinal
+ *     22        max |R[13..15] - v_ref|^2, summed as (x x + y y) + z z
+ *     23        max |R[16..18]|^2, summed in the same order
+ *     24        ordinal of the first fallen record
+ *     25        ordinal of the last record NOT in band
+ *     26        count of in-band records
+ *     27        max over records and joints of |R[19 + j]|, j = 0..11
+ *     28        sum over records of e, e the twelve squared torques R[19 + j]^2 added in ascending j
+ *     29        max of the QP's f_z over the feet (R[33], R[36], R[39], R[42])
+ *     30        min foot height R[47 + i] over records and feet with desired contact R[43 + i] == 1
+ *     32        count of records whose four desired-contact flags R[43..46] differ from those of the record folded before it (among the records that
+ *               take part)
+ *     33..36    the flags folded last: the carry; the first record that takes part sets it and counts no switch
+ *     37..40    per foot, count of records with flag 1
+ *     41        max foot height over records and feet with flag 0
+ *     42        0
+ *     43..50    of the records with plant kind R[57] == 1 only:
+ *       43      their count
+ *       44      count of those with clamped joints, R[58] > 0
+ *       45      sum of R[58]
+ *       46      max R[59]
+ *       47      min R[60]
+ *       48      count of those with R[60] < 0: a held foot pulls (without a ground, the reason to discard the run)
+ *       49, 50  max R[61], max R[62]
+ *     51..61    of the records with a ground word, 4096 <= R[63] < 8192, word = R[63] - 4096, only:
+ *       51      their count
+ *       52..55  per foot i, count of records with word bit i (ground contact)
+ *       56      sum over records of the number of slip bits 4..7 set
+ *       57      sum over records of the number of plan-against-ground bits 8..11 set
+ *       58      count of records with bits 0..3 all clear (airborne)
+ *       59      ordinal k of the first record with a slip bit
+ *       60      count of records whose bits 0..3 differ from those of the ground record folded before it
+ *       61      those four bits of the ground record folded last as a number 0..15: the carry; the first ground record sets it and counts no switch
+ *     62, 63    0
+ * Derived, as for the rollout summaries: "settled from" = field 25 + 1; an instance is SETTLED if field 24 < 0 and field 25 < field 0 - 1; it has
+ * FALLEN if field 24 >= 0.
+ *
+ * One study record, SRBM_TICK_STUDY_DOUBLES doubles, of summaries[instances][64] taken in ascending instance order:
+ *     0         instances
+ *     1, 2      number fallen, number settled
+ *     3         number with summary field 7 > 0
+ *     4, 5      max (-1 where none is settled) and sum of "settled from" over the settled instances
+ *     6, 7, 8   max of summary field 18, of field 20, of field 27
+ *     9, 10     sum of summary field 9, of field 44
+ *     11        number with summary field 48 > 0
+ *     12..14    sum of summary field 56, of field 57, of field 15
+ *     15        min of summary field 47
+ *
+ * The entries are those of the rollout summaries, on the tick log.  srbm_tick_summary_enable: criteria[8] and ref[batch][6]; allocates the summaries
+ * and resets them; criteria == NULL disables them and frees the buffers.  srbm_tick_summary_fold folds the tick-log slots [first_slot, first_slot +
+ * count), which must lie in [0, ticks_logged), asynchronously on the batch's stream: a logged srbm_controller_advance, a fold and srbm_tick_log_reset
+ * need no host synchronisation between them.  srbm_tick_summary_fold_dev runs the same kernel on any device array log_dev[slots][batch][64] of tick
+ * records (a host-driven chain, tests); it needs no tick log.  _get (synchronous), _copy_dev, srbm_tick_study (synchronous), srbm_tick_study_dev and
+ * srbm_tick_summary_allgather_dev (declared with the multi-GPU entries below) are their srbm_rollout_* counterparts.  srbm_tick_fold_host and
+ * srbm_tick_study_host run the same fold of one record and the same reduction compiled for the host, on host arrays: log[slots][batch][64],
+ * summaries[batch][64] in and out (the caller sets them to the reset state above); no GPU, no batch.
+ * Refused before anything is queued, the batch and the summaries untouched, srbm_last_error naming the case: no tick log enabled; no tick summary
+ * enabled; a slot or instance range outside what exists; NULL where it is not allowed; a criterion that is not finite; a reserved criterion other
+ * than 0.  A clone has tick summaries off, as it has logging off. */
+#define SRBM_TICK_SUMMARY_DOUBLES 64
+#define SRBM_TICK_CRITERIA_DOUBLES 8
+#define SRBM_TICK_REF_DOUBLES 6
+#define SRBM_TICK_STUDY_DOUBLES 16
+int srbm_tick_summary_doubles(void);                           /* SRBM_TICK_SUMMARY_DOUBLES; callable without a GPU */
+int srbm_tick_summary_enable(srbm_batch* h, const double* criteria, const double* ref);
+int srbm_tick_summary_reset(srbm_batch* h);
+int srbm_tick_summary_fold(srbm_batch* h, int first_slot, int count);
+int srbm_tick_summary_fold_dev(srbm_batch* h, const double* log_dev, int slots, int first_slot, int count);
+int srbm_tick_summary_get(srbm_batch* h, int first, int count, double* out);
+int srbm_tick_summary_copy_dev(srbm_batch* h, double* out_dev);
+int srbm_tick_study(srbm_batch* h, double* study);
+int srbm_tick_study_dev(srbm_batch* h, const double* summaries_dev, int instances, double* study_dev);
+int srbm_tick_fold_host(const double* log, int slots, int batch, int first_slot, int count, const double* criteria, const double* ref, double* summaries);
+int srbm_tick_study_host(const double* summaries, int instances, double* study);
+
 /* ---- the torque-driven whole-body plant ----
  * The plant above integrates the QP's own accelerations: the torques and joint targets of the control action act on nothing, and the robot is exactly
  * the controller's model.  The torque-driven plant (kind 1) takes the control action and computes its own accelerations, per sub-step of h / S
@@ -795,6 +904,8 @@ typedef struct ncclComm* ncclComm_t;               /* identical to the typedef i
 int srbm_allgather_results(srbm_batch* h, ncclComm_t comm, double* out_dev);
 /* the same for the rollout summaries (see "rollout summaries" above): out_dev[world * batch][SRBM_ROLLOUT_SUMMARY_DOUBLES] */
 int srbm_rollout_allgather_dev(srbm_batch* h, ncclComm_t comm, double* out_dev);
+/* ... and for the tick summaries (see "tick summaries" above): out_dev[world * batch][SRBM_TICK_SUMMARY_DOUBLES] */
+int srbm_tick_summary_allgather_dev(srbm_batch* h, ncclComm_t comm, double* out_dev);
 /* ncclGetUniqueId on one rank (bytes travel to the others by whatever the host uses for its rendezvous), ncclCommInitRank on the batch's device, ncclCommDestroy */
 int srbm_rccl_get_unique_id(void* id_bytes);
 int srbm_rccl_comm_init_rank(srbm_batch* h, int world, int rank, const void* id_bytes, ncclComm_t* comm_out);
