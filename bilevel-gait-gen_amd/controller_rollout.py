@@ -15,6 +15,8 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     mpc.plant_set_push(time, impulse)     optional: one push per instance
     R.set_plant(1, kp, kd, limit, 4)      optional: the torque-driven plant, 4 sub-steps per tick; R.set_plant_bodies(...): its own bodies
     R.set_ground(ground)                  optional, with set_plant(1, ...): a compliant ground [batch][8] under the torque-driven plant's feet
+    R.set_terrain([terrain_patch(gx=0.1, mu=0.6), terrain_patch(x=(0.5, 1.0), gx=0.1, mu=0.1)])
+                                          optional, with a ground: sloped patches with a friction coefficient each in place of its plane
     R.tick_log_enable(200)                optional: one record per tick and instance
     R.set_contact_feedback(True)          optional, with a ground: early touch-downs re-time the plan before every MPC update
     R.advance(0, 200, 50, 1e-3)           200 ticks of 1 ms, an MPC update every 50; asynchronous
@@ -38,6 +40,7 @@ GROUND_PLANT_LOG_FIELDS = dict(plant_kind=57, clamped_joints=58, torque_deviatio
                                ground_word=63)
 GROUND_WORD_OFFSET = 4096
 GROUND_DOUBLES, CONTACT_STATE_DOUBLES = 8, 12
+TERRAIN_PATCHES, TERRAIN_DOUBLES = 8, 8      # host.TERRAIN_PATCHES, host.TERRAIN_DOUBLES: the most patches per instance, the doubles of a patch
 CONTACT_FEEDBACK_DOUBLES = 8        # the feedback record of an instance: per foot {touch-downs moved, time of the last move (-1: none)}
 FLAG_PUSH, FLAG_UPDATE, FLAG_COAST, FLAG_BREAKDOWN = 1, 2, 4, 8
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
@@ -55,6 +58,12 @@ def decode_ground_word(field63):
     word = np.where(ground, w - GROUND_WORD_OFFSET, 0)
     bits = lambda first: ((word[..., None] >> (first + np.arange(4))) & 1).astype(bool)
     return dict(ground=ground, in_contact=bits(0), slipping=bits(4), plan_differs=bits(8))
+
+
+def terrain_patch(x=(-np.inf, np.inf), y=(-np.inf, np.inf), z0=0.0, gx=0.0, gy=0.0, mu=0.6):
+    """one patch of a terrain -> [8] = x_min, x_max, y_min, y_max, z0, gx, gy, mu: the rectangle x, y in world coordinates (unbounded by default),
+    the surface z = z0 + gx x + gy y through the world origin, the friction coefficient.  x = (1, 0) makes an empty patch"""
+    return np.array([x[0], x[1], y[0], y[1], z0, gx, gy, mu], float)
 
 
 class ControllerRollout:
@@ -158,8 +167,21 @@ class ControllerRollout:
         m = self.mpc
         m._chk(self.L.srbm_wb_plant_set_ground(m.h, None if ground is None else _d(m._bcast(ground, GROUND_DOUBLES))))
 
+    def set_terrain(self, terrain):
+        """a terrain for the ground (set_ground first): [P][8] for every instance or [batch][P][8], 1 <= P <= TERRAIN_PATCHES, the rows as
+        terrain_patch makes them; later patches lie over earlier ones.  None removes it (the ground is its plane again)"""
+        m = self.mpc
+        if terrain is None:
+            m._chk(self.L.srbm_wb_plant_set_terrain(m.h, None, 0))
+            return
+        t = np.asarray(terrain, float)
+        if t.ndim not in (2, 3) or t.shape[-1] != TERRAIN_DOUBLES or (t.ndim == 3 and t.shape[0] != m.batch):
+            raise ValueError('a terrain is [patches][%d] or [batch][patches][%d]' % (TERRAIN_DOUBLES, TERRAIN_DOUBLES))
+        t = np.ascontiguousarray(np.broadcast_to(t, (m.batch,) + t.shape[-2:]))
+        m._chk(self.L.srbm_wb_plant_set_terrain(m.h, _d(t if t.size else np.zeros(1)), int(t.shape[1])))       # (no patches: refused there, not NULL)
+
     def contact_state(self):
-        """-> cs[batch][4][3]: per foot in_contact (0 | 1), anchor_x, anchor_y, after the work queued so far"""
+        """-> cs[batch][4][3]: per foot in_contact (0 | 1; with a terrain 1 + the patch), anchor_x, anchor_y, after the work queued so far"""
         m = self.mpc
         cs = np.zeros((m.batch, 4, 3))
         m._chk(self.L.srbm_wb_plant_get_contact_state(m.h, _d(cs)))

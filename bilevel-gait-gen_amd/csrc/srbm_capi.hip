@@ -23,6 +23,7 @@
 #include "srbm_wb_plant.hiph"
 #include "srbm_wb_fd.hiph"
 #include "srbm_wb_ground.hiph"
+#include "srbm_wb_terrain.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_tick_summary.hiph"
@@ -120,6 +121,9 @@ struct srbm_batch {
     // the ground of the torque-driven plant (srbm_wb_ground.hiph)
     double* d_ground = nullptr;      // [batch][WBG_GROUND_DOUBLES]; nullptr: no ground, kind 1 holds the planned feet (srbm_wb_plant_set_ground)
     double* d_cs = nullptr;          // the contact state [batch][WBG_CS_DOUBLES], allocated with d_wb
+    // the terrain of that ground (srbm_wb_terrain.hiph)
+    double* d_terrain = nullptr;     // [batch][WBG_TERRAIN_PATCHES][WBT_PATCH_DOUBLES]; nullptr: the ground is its plane (srbm_wb_plant_set_terrain)
+    int terrain_patches = 0;         // the n_patches of the call that set it: what in_contact may hold
     // contact feedback of the rollout's MPC update (srbm_contact_feedback.hiph)
     int contact_fb = 0;              // 1: the update ticks of srbm_controller_advance run the feedback kernel (srbm_controller_set_contact_feedback)
     double* d_fb = nullptr;          // the feedback record [batch][SRBM_FB_DOUBLES], allocated with d_wb
@@ -460,7 +464,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_wb); (void)hipFree(h->d_wb_int); (void)hipFree(h->d_tlog);
     (void)hipFree(h->d_tsum); (void)hipFree(h->d_tsum_ref);
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
-    (void)hipFree(h->d_ground); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
+    (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -644,6 +648,10 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     // (... and its ground; the contact state went with (q, v))
     if (ok && src->d_ground)
         ok = hipMalloc(&h->d_ground, sizeof(double) * WBG_GROUND_DOUBLES * B) == hipSuccess && cp(h->d_ground, src->d_ground, sizeof(double) * WBG_GROUND_DOUBLES * B);
+    // (... and the ground's terrain)
+    h->terrain_patches = src->terrain_patches;
+    if (ok && src->d_terrain)
+        ok = hipMalloc(&h->d_terrain, sizeof(double) * WBT_INSTANCE_DOUBLES * B) == hipSuccess && cp(h->d_terrain, src->d_terrain, sizeof(double) * WBT_INSTANCE_DOUBLES * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2317,7 +2325,9 @@ static int fd_usable(srbm_batch* h, const char* fn) {
     return 0;
 }
 // the torque-driven plant step of tick `tick` on the batch's stream: on the ground with the contact state cs, with the feet of `contact` held where
-// cs is nullptr; contact (on a ground: the plan's) and qp_sol are the tick's, for the record; lg: the record of the tick, nullptr: the unlogged kernel
+// cs is nullptr; contact (on a ground: the plan's) and qp_sol are the tick's, for the record; lg: the record of the tick, nullptr: the unlogged kernel.
+// On a ground with a terrain in force (terrain_in_force) the step is the terrain's
+static bool terrain_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_ground && h->d_terrain; }
 static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
                             const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
     const double* push = h->push_set ? h->d_push : nullptr;
@@ -2327,7 +2337,11 @@ static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, 
     const SrbmGroundArgs ga{h->d_ground, cs};
     const SrbmTickLogArgs l = lg ? *lg : SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0};
     const dim3 grid(h->batch), block(WBC_THREADS);
-    if (cs && lg) hipLaunchKernelGGL((srbm_k_wb_ground_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, l);
+    if (cs && terrain_in_force(h)) {
+        if (lg) hipLaunchKernelGGL((srbm_k_wb_terrain_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, tick, tick_dt, push, q, v, status, time_next, l);
+        else hipLaunchKernelGGL((srbm_k_wb_terrain_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, tick, tick_dt, push, q, v, status, time_next, l);
+    }
+    else if (cs && lg) hipLaunchKernelGGL((srbm_k_wb_ground_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, l);
     else if (cs) hipLaunchKernelGGL((srbm_k_wb_ground_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, tick, tick_dt, push, q, v, status, time_next, l);
     else if (lg) hipLaunchKernelGGL((srbm_k_wb_fd_step<true>), grid, block, 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, l);
     else hipLaunchKernelGGL((srbm_k_wb_fd_step<false>), grid, block, 0, h->stream, h->dp, fa, tick, tick_dt, push, q, v, status, time_next, l);
@@ -2406,6 +2420,56 @@ int srbm_wb_plant_set_ground(srbm_batch* h, const double* ground) {
     HIPCHK(hipMemcpyAsync(h->d_ground, c.host(a), a.bytes(), hipMemcpyHostToDevice, h->stream));
     return srbm_synchronize(h);
 }
+static_assert(SRBM_TERRAIN_PATCHES == WBG_TERRAIN_PATCHES && SRBM_TERRAIN_DOUBLES == WBG_TERRAIN_DOUBLES, "include/srbm_rti.h states the terrain's sizes");
+// the terrain of the ground (srbm_wb_terrain.hiph): validated, the unit normals formed here in double, the unused records empty
+int srbm_wb_plant_set_terrain(srbm_batch* h, const double* terrain, int n_patches) {
+    const std::string fn = "srbm_wb_plant_set_terrain";
+    if (!h) return fail(fn + ": bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (!terrain) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->d_terrain) HIPCHK(hipFree(h->d_terrain));
+        h->d_terrain = nullptr; h->terrain_patches = 0;
+        return 0;
+    }
+    if (n_patches < 1 || n_patches > WBG_TERRAIN_PATCHES)
+        return fail(fn + ": n_patches " + std::to_string(n_patches) + " is not in 1.." + std::to_string(WBG_TERRAIN_PATCHES));
+    if (!h->d_ground) return fail(fn + ": a terrain is a setting of the ground, and the torque-driven plant has none (srbm_wb_plant_set_ground)");
+    const size_t B = h->batch, P = n_patches;
+    static const char* const names[WBG_TERRAIN_DOUBLES] = {"x_min", "x_max", "y_min", "y_max", "the height z0 at the world origin", "the slope gx", "the slope gy",
+                                                           "the friction coefficient"};
+    for (size_t e = 0; e < WBG_TERRAIN_DOUBLES * P * B; e++) {
+        const int f = (int)(e % WBG_TERRAIN_DOUBLES);
+        const double x = terrain[e];
+        const std::string at = fn + ": instance " + std::to_string(e / (WBG_TERRAIN_DOUBLES * P)) + ", patch " + std::to_string(e / WBG_TERRAIN_DOUBLES % P) + ", field " +
+                               std::to_string(f) + " (" + names[f] + "): ";
+        if (std::isnan(x)) return fail(at + "is NaN");
+        if (f >= 4 && !std::isfinite(x)) return fail(at + "must be finite");
+        if (f == 7 && x < 0.0) return fail(at + "must be >= 0");
+    }
+    Carve c;
+    const auto a = c.add<double>(WBT_INSTANCE_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    double* rec = c.host(a);
+    for (size_t b = 0; b < B; b++)
+        for (size_t t = 0; t < WBG_TERRAIN_PATCHES; t++) {
+            double* r = rec + (b * WBG_TERRAIN_PATCHES + t) * WBT_PATCH_DOUBLES;
+            std::memset(r, 0, sizeof(double) * WBT_PATCH_DOUBLES);
+            if (t >= P) { r[0] = 1.0; r[2] = 1.0; r[10] = 1.0; continue; }          // empty: x_min > x_max
+            std::memcpy(r, terrain + (b * P + t) * WBG_TERRAIN_DOUBLES, sizeof(double) * WBG_TERRAIN_DOUBLES);
+            const double gx = r[5], gy = r[6];
+            const double gxx = gx * gx;
+            const double gyy = gy * gy;
+            const double s1 = 1.0 + gxx;
+            const double s2 = s1 + gyy;
+            const double s = std::sqrt(s2);
+            r[8] = -gx / s; r[9] = -gy / s; r[10] = 1.0 / s;
+        }
+    if (!h->d_terrain) HIPCHK(hipMalloc(&h->d_terrain, a.bytes()));
+    h->terrain_patches = n_patches;
+    HIPCHK(hipMemcpyAsync(h->d_terrain, rec, a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
 int srbm_wb_plant_get_contact_state(srbm_batch* h, double* cs) {
     if (!h || !cs) return fail("srbm_wb_plant_get_contact_state: bad arguments");
     if (!h->d_wb) return fail(WB_NO_STATE);
@@ -2418,7 +2482,11 @@ int srbm_wb_plant_set_contact_state(srbm_batch* h, const double* cs) {
     const size_t B = h->batch;
     for (size_t e = 0; e < WBG_CS_DOUBLES * B; e++) {
         const std::string at = fn + ": instance " + std::to_string(e / WBG_CS_DOUBLES) + ", foot " + std::to_string(e % WBG_CS_DOUBLES / 3) + ": ";
-        if (e % 3 == 0) { if (cs[e] != 0.0 && cs[e] != 1.0) return fail(at + "in_contact must be 0 or 1"); }
+        if (e % 3 == 0) {
+            if (!h->d_terrain) { if (cs[e] != 0.0 && cs[e] != 1.0) return fail(at + "in_contact must be 0 or 1"); }
+            else if (!(cs[e] >= 0.0 && cs[e] <= (double)h->terrain_patches && cs[e] == std::floor(cs[e])))
+                return fail(at + "in_contact must be 0, or 1 + the patch: an integer 0.." + std::to_string(h->terrain_patches) + " while a terrain is set");
+        }
         else if (!std::isfinite(cs[e])) return fail(at + "the anchor is not finite");
     }
     HIPCHK(hipSetDevice(h->device));
@@ -2440,8 +2508,12 @@ int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double
     if (ground_usable(h, "srbm_wb_ground_dynamics") || use_batch(h)) return -1;
     int stride = 0;
     const SrbmBody* bodies = fd_bodies(h, &stride);
-    hipLaunchKernelGGL(srbm_k_wb_ground_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_ground, q_dev, v_dev, tau_dev, cs_in_dev,
-                       sol_dev, cs_out_dev, status_dev);
+    if (terrain_in_force(h))
+        hipLaunchKernelGGL(srbm_k_wb_terrain_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_ground, h->d_terrain, q_dev, v_dev,
+                           tau_dev, cs_in_dev, sol_dev, cs_out_dev, status_dev);
+    else
+        hipLaunchKernelGGL(srbm_k_wb_ground_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_ground, q_dev, v_dev, tau_dev, cs_in_dev,
+                           sol_dev, cs_out_dev, status_dev);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -578,7 +578,8 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *       62      |F_plant - F_QP|_inf over the stance feet
  *       63      0
  *     Plant kind 1 with a ground set (srbm_wb_plant_set_ground, below), 58..63 from the LAST sub-step of the tick: 57..59 as above, and
- *       60      the smallest vertical ground force over the feet the plan holds in stance, 0 if it holds none; >= 0 by construction
+ *       60      the smallest vertical ground force over the feet the plan holds in stance, 0 if it holds none; >= 0 by construction (with a terrain
+ *               in force, srbm_wb_plant_set_terrain: the smallest NORMAL force)
  *       61      |a_plant - a_QP|_inf over the 18 accelerations
  *       62      |F_ground - F_QP|_inf over all four feet, the QP's force zero for a foot out of the plan (as in fields 31..42)
  *       63      4096 + word.  Bit i: foot i in ground contact; bit 4 + i: foot i slipping; bit 8 + i: the plan's contact flag of foot i
@@ -775,8 +776,8 @@ int srbm_wb_fd_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, 
  *     v <- v + (h / S) a,  q <- pinocchio::integrate(q, v, h / S);  the push where kind 1 applies it
  * cs is carried from sub-step to sub-step and, in the batch, from tick to tick.  A sub-step whose factorisation meets a pivot that is not finite or not
  * positive takes a = 0 and reports (a, F) = 0 (flags bit 3 of the tick); its contact state is what the law left.
- * What it is NOT: compliant, not rigid (a foot that carries N sinks by N / k_n); no impact law; no LCP; no terrain but one horizontal plane per
- * instance.  The plan is told of the ground's contacts only with srbm_controller_set_contact_feedback on (below: MPC::AdjustForCurrentContacts before
+ * What it is NOT: compliant, not rigid (a foot that carries N sinks by N / k_n); no impact law; no LCP; one horizontal plane per instance
+ * (sloped patches with a friction coefficient each: srbm_wb_plant_set_terrain, below).  The plan is told of the ground's contacts only with srbm_controller_set_contact_feedback on (below: MPC::AdjustForCurrentContacts before
  * every MPC update); off, the default, the controller keeps believing its plan.  Tick log fields 43..46 against field 63 show where the plan and the
  * ground disagree.
  *
@@ -801,6 +802,53 @@ int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double
  * srbm_controller_advance launches this kernel on the batch's (q, v, cs) when the kind is 1 and a ground is set; nothing else in it changes. */
 int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_dev, double* v_dev, double* cs_dev, const double* control_dev,
                             const int* status_dev, double* sol_dev);
+
+/* ---- a terrain for that ground: sloped patches, friction per patch ----
+ * A terrain is a SETTING of the ground, as the ground is a setting of plant kind 1: a list of rectangular patches per instance, each with a plane
+ * of its own and a friction coefficient of its own.  Contact is resolved along the patch normal, friction acts in the patch's tangent plane.
+ * terrain[batch][n_patches][8], 1 <= n_patches <= SRBM_TERRAIN_PATCHES, per patch:
+ *     0..3  x_min, x_max, y_min, y_max   the rectangle in world x, y; may be -inf / +inf; x_min > x_max: the patch is empty (how an instance uses
+ *                                        fewer patches than the batch)
+ *     4     z0                           finite: the surface is z = z0 + gx x + gy y in world coordinates, through the world origin (no reference
+ *     5, 6  gx, gy                       finite   point, so an unbounded patch is well defined)
+ *     7     mu                           finite, >= 0
+ * The unit normal n = (nx, ny, nz) of a patch is formed once, when the terrain is set, in double: s = sqrt((1 + gx gx) + gy gy), nx = -gx / s,
+ * ny = -gy / s, nz = 1 / s.  The ground's k_n, d_n, k_t, d_t (ground[b][1, 2, 4, 5]) stay the compliance of every patch and ground[b][0] = -inf still
+ * means "nothing under this instance"; with a terrain set the ground's own z0 (other than as that switch) and mu are not used.
+ * The contact state keeps its shape cs[batch][12]; with a terrain in_contact holds 1 + j, j the patch the foot is on, instead of 1 (every reader
+ * tests != 0: contact feedback, the word of tick log field 63).  The stored patch number is only ever compared, never used as an index.
+ * Per sub-step and foot i, p and w = J_i v as on the ground; every line is one rounded operation, sums associate as written:
+ *     j = the LAST patch t with x_min <= p.x <= x_max and y_min <= p.y <= y_max (later patches lie over earlier ones); none: air
+ *     hx = gx p.x; hy = gy p.y; h0 = z0 + hx; zp = h0 + hy; dz = zp - p.z; delta = nz dz
+ *     !(delta > 0): air  ->  F = 0, in_contact = 0, anchor = (0, 0)
+ *     first = (in_contact after the previous sub-step) != 1 + j          (not in contact, or in contact with another patch: re-anchored)
+ *     wn = (nx wx + ny wy) + nz wz;   wt = w - wn n
+ *     ns = k_n delta; nd = d_n wn; n1 = ns - nd; N = fmax(0, n1)
+ *     pb = p + delta n                                                    (the foot projected onto the surface)
+ *     A  = pb if first, else (ax, ay, (z0 + gx ax) + gy ay)
+ *     e  = p - A;  en = (nx ex + ny ey) + nz ez;  et = e - en n
+ *     sv = k_t et; dv = d_t wt; T0 = -sv - dv;  lim = mu N;  nn = (T0x T0x + T0y T0y) + T0z T0z;  n0 = sqrt(nn)
+ *     n0 <= lim:  T = T0,              anchor = (A.x, A.y)                (stick)
+ *     else:       sc = lim / n0; T = sc T0; u = T + dv; qv = u / k_t; anchor = (pb.x + qv.x, pb.y + qv.y)     (slip)
+ *     F = T + N n  (world components);  in_contact = 1 + j
+ * then the ground's solve M a = S' tau - C v - g + sum_i J_i' F_i, its integration and its push, unchanged.  On one unbounded level patch,
+ * n = (-0, -0, 1), every statement returns the bits of the plane's law: the terrain is that law generalised, not a second one.
+ * The tick record with a terrain in force: fields 0..59, 61, 62 as on the ground (forces in world components); field 60 is the smallest NORMAL
+ * force N over the feet the plan holds (today's value on a level patch; >= 0 by construction); field 63 has the ground's format 4096 + word, so the
+ * tick summaries fold terrain rollouts unchanged.
+ * What it is NOT: no side faces -- a foot that crosses the edge of a raised patch below its surface is at once delta deep in it and is pushed out
+ * with k_n delta, so join levels with ramps or keep steps small; still compliant; no impact law; no edges, curvature or rolling contact; the
+ * controller is told nothing of the terrain (contact feedback apart).
+ *
+ * srbm_wb_plant_set_terrain: NULL removes the terrain.  A terrain needs a ground: setting one without a ground is refused; removing the ground
+ * removes nothing else, and the terrain is ignored while no ground is set or the kind is 0, as the ground is ignored under kind 0.  With kind 1, a
+ * ground and a terrain all set, srbm_controller_advance, srbm_gait_controller_advance, srbm_wb_ground_dynamics[_dev] and srbm_wb_ground_step_dev run
+ * the terrain's kernels (csrc/srbm_wb_terrain.hiph); they are to the terrain what they are to the ground.  Refused, naming instance, patch and field,
+ * the batch untouched: NaN anywhere; z0, gx, gy, mu not finite; mu < 0; n_patches out of range.  While a terrain is set,
+ * srbm_wb_plant_set_contact_state accepts the integers 0..n_patches for in_contact.  srbm_batch_clone carries the terrain. */
+#define SRBM_TERRAIN_PATCHES 8
+#define SRBM_TERRAIN_DOUBLES 8
+int srbm_wb_plant_set_terrain(srbm_batch* h, const double* terrain, int n_patches);
 
 /* ---- the MPC update of the rollout in full: MPCController::MPCUpdate (controllers/mpc_controller.cpp:299-346) ----
  * Step 3 of srbm_controller_advance is MPC::GetRealTimeUpdate alone.  The reference's update does two more things, both off by default here.

@@ -10,6 +10,10 @@ medians and spreads.
   (e) ground     (d) with a compliant ground set (srbm_wb_plant_set_ground: k_n 2e4, d_n 100, mu 0.7, k_t 1e4, d_t 50, the plane 3 mm above each
                  instance's lowest foot at the start), logged, S = 1 and 4; beside (d) this is what the ground costs.  And its step kernel alone
                  (srbm_wb_ground_step_dev, S = 1 and 4), as (c)
+  (t) terrain    (e) at S = 4 with a terrain of 8 patches set (srbm_wb_plant_set_terrain: the ground's plane as patch 0 and over it seven strips 0.1 m
+                 wide in x, sloped by +-1 % about their centre lines, friction 0.7 and 0.4 in turn), logged; beside (e) this is what the terrain
+                 costs.  And its step kernel alone, S = 1 and 4, interleaved with the ground step kernel alone on the same inputs.  Skipped, with
+                 a note in the output, on a library that has no terrain (a parent's build run from a copy of its tree)
   (f) feedback   (e) at S = 4 with contact feedback on (srbm_controller_set_contact_feedback: one small launch per MPC update); beside (e) this is
                  what the feedback costs -- per update: the difference times ticks_per_update
   (g) gait       (e) at S = 4 through srbm_gait_controller_advance with gait_opt_freq 5, feedback off, 250 ticks so that the updates are three plain
@@ -51,7 +55,10 @@ def main():
     res = {'entry': [], 'entry_logged': [], 'chain': [], 'plant': [], 'torque_s1_logged': [], 'torque_s4_logged': [], 'fd_step_s1': [], 'fd_step_s4': [],
            'ground_s1_logged': [], 'ground_s4_logged': [], 'ground_step_s1': [], 'ground_step_s4': [], 'ground_s4_feedback_logged': [],
            'ground_s4_gait_f5_logged': []}
-    ground = None
+    has_terrain = hasattr(ControllerRollout, 'set_terrain')
+    if has_terrain:
+        res.update({'terrain_s4_logged': [], 'terrain_step_s1': [], 'terrain_step_s4': []})
+    ground = terrain = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
     f64 = dict(dtype=torch.float64, device='cuda')
@@ -118,12 +125,42 @@ def main():
             word = decode_ground_word(log[:, :, G['ground_word']])
             info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
                               zero_action_ticks=int((log[:, :, G['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, G['qp_iters']].mean()),
+                              slowest_qp_iterations_mean=float(log[:, :, G['qp_iters']].max(axis=1).mean()),
                               breakdown_ticks=int(((log[:, :, G['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
                               clamped_ticks=int((log[:, :, G['clamped_joints']] > 0).sum()),
                               min_planned_stance_fz=float(log[:, :, G['min_planned_stance_fz']].min()),
                               feet_in_contact_mean=float(word['in_contact'].sum(axis=-1).mean()), slipping_feet_mean=float(word['slipping'].sum(axis=-1).mean()),
                               feet_off_the_plan_mean=float(word['plan_differs'].sum(axis=-1).mean()),
                               median_accel_mismatch=float(np.median(log[:, :, G['accel_mismatch']])))
+        # (t) ... with a terrain of 8 patches
+        if has_terrain:
+            if terrain is None:
+                terrain = np.zeros((B, 8, 8))
+                x0 = q0[:, 0] - 0.35
+                for b in range(B):
+                    terrain[b, 0] = [-np.inf, np.inf, -np.inf, np.inf, ground[b, 0], 0.0, 0.0, 0.7]
+                    for t in range(1, 8):
+                        lo, gx = x0[b] + 0.1 * (t - 1), 0.01 * (-1) ** t
+                        terrain[b, t] = [lo, lo + 0.1, -np.inf, np.inf, ground[b, 0] - gx * (lo + 0.05), gx, 0.0, 0.7 if t % 2 else 0.4]
+            g, R = fresh(TICKS + 3)
+            R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
+            R.set_ground(ground)
+            R.set_terrain(terrain)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res['terrain_s4_logged'].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log = R.tick_log()
+            word = decode_ground_word(log[:, :, G['ground_word']])
+            info['terrain_s4_logged'] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
+                                             zero_action_ticks=int((log[:, :, G['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, G['qp_iters']].mean()),
+                              slowest_qp_iterations_mean=float(log[:, :, G['qp_iters']].max(axis=1).mean()),
+                                             clamped_ticks=int((log[:, :, G['clamped_joints']] > 0).sum()), patches_stood_on=sorted(set(R.contact_state()[:, :, 0].ravel().tolist())),
+                                             breakdown_ticks=int(((log[:, :, G['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
+                                             min_planned_stance_normal_force=float(log[:, :, G['min_planned_stance_fz']].min()),
+                                             feet_in_contact_mean=float(word['in_contact'].sum(axis=-1).mean()),
+                                             slipping_feet_mean=float(word['slipping'].sum(axis=-1).mean()),
+                                             feet_off_the_plan_mean=float(word['plan_differs'].sum(axis=-1).mean()))
         # (f) ... with contact feedback on
         g, R = fresh(TICKS + 3)
         R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
@@ -209,8 +246,18 @@ def main():
                 ground_step()
                 signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
                 res['ground_step_s%d' % S].append(timed(g, ground_step))
+                if has_terrain:         # ... and the terrain step kernel alone: the same entry with the terrain in force, from the same start
+                    R.set_terrain(terrain)
+                    q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64)); cs_d.zero_()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    ground_step()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    res['terrain_step_s%d' % S].append(timed(g, ground_step))
+                    R.set_terrain(None)
     signal.setitimer(signal.ITIMER_REAL, 0)
     med = {k: float(np.median(v)) for k, v in res.items()}
+    if not has_terrain:
+        info['terrain'] = 'this library has no terrain: rows (t) skipped'
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
                           spread_ms={k: float(max(v) - min(v)) for k, v in res.items()}, **info)))
 
