@@ -21,7 +21,9 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.set_contact_feedback(True)          optional, with a ground: early touch-downs re-time the plan before every MPC update
     R.advance(0, 200, 50, 1e-3)           200 ticks of 1 ms, an MPC update every 50; asynchronous
     R.advance(0, 200, 50, 1e-3, gait=go, gait_opt_freq=5)      the same with the gait step of host.BatchGaitOptimizer `go` in the updates
-    q, v = R.state(); log = R.tick_log()"""
+    R.set_latency(0.02)                   optional: every update comes into force 20 ms after it started, not at the next tick; per instance:
+                                          R.set_latency(base[batch], per_iteration) -- base + per_iteration * (IPM iterations of the solve)
+    q, v = R.state(); log = R.tick_log(); pub = R.latency_record()"""
 import ctypes as C
 
 import numpy as np
@@ -43,6 +45,9 @@ GROUND_DOUBLES, CONTACT_STATE_DOUBLES = 8, 12
 TERRAIN_PATCHES, TERRAIN_DOUBLES = 8, 8      # host.TERRAIN_PATCHES, host.TERRAIN_DOUBLES: the most patches per instance, the doubles of a patch
 CONTACT_FEEDBACK_DOUBLES = 8        # the feedback record of an instance: per foot {touch-downs moved, time of the last move (-1: none)}
 FLAG_PUSH, FLAG_UPDATE, FLAG_COAST, FLAG_BREAKDOWN = 1, 2, 4, 8
+LATENCY_RECORD_DOUBLES = 8          # the latency record of an instance (set_latency), field name -> index
+LATENCY_RECORD_FIELDS = dict(update_in_force=0, publications=1, overruns=2, last_publication_time=3, t_start_in_force=4, last_latency=5, max_latency=6,
+                             age_sum=7)
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
 
 
@@ -64,6 +69,24 @@ def terrain_patch(x=(-np.inf, np.inf), y=(-np.inf, np.inf), z0=0.0, gx=0.0, gy=0
     """one patch of a terrain -> [8] = x_min, x_max, y_min, y_max, z0, gx, gy, mu: the rectangle x, y in world coordinates (unbounded by default),
     the surface z = z0 + gx x + gy y through the world origin, the friction coefficient.  x = (1, 0) makes an empty patch"""
     return np.array([x[0], x[1], y[0], y[1], z0, gx, gy, mu], float)
+
+
+def publish_ticks(L, first_tick, ticks, ticks_per_update, tick_dt, base, per_iteration, iters):
+    """the publication ticks of a rollout with a latency set, on the host (srbm_latency_publish_ticks_host; L: the loaded library, host.lib()).
+    iters[batch][n_updates]: the IPM iterations of update u = 1 .. n_updates of every instance; base, per_iteration: one number or [batch].
+    -> tick[batch][n_updates], overrun[batch][n_updates]: the tick before which update u is published and whether by force before it was due, for
+    the publications among ticks first_tick .. first_tick + ticks - 1 of a rollout from tick 0; -1 and 0 for the others"""
+    iters = np.ascontiguousarray(iters, dtype=np.int32)
+    if iters.ndim != 2:
+        raise ValueError('iters is [batch][n_updates]')
+    batch, n = iters.shape
+    lat = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(base, float), (batch,)), np.broadcast_to(np.asarray(per_iteration, float), (batch,))], axis=1))
+    tick, over = np.zeros((batch, n), np.int32), np.zeros((batch, n), np.int32)
+    if L.srbm_latency_publish_ticks_host(batch, int(first_tick), int(ticks), int(ticks_per_update), float(tick_dt), _d(lat),
+                                         (iters if iters.size else np.zeros(1, np.int32)).ctypes.data_as(_ip), n, (tick if n else np.zeros(1, np.int32)).ctypes.data_as(_ip),
+                                         (over if n else np.zeros(1, np.int32)).ctypes.data_as(_ip)) != 0:
+        raise RuntimeError('srbm: ' + L.srbm_last_error().decode())
+    return tick, over
 
 
 class ControllerRollout:
@@ -124,6 +147,39 @@ class ControllerRollout:
         """the plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from qp_sol[batch][30], status[batch][2] of
         control_tick_dev; asynchronous, never logs"""
         self.mpc._chk(self.L.srbm_wb_plant_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, qp_sol, status))
+
+    # ---- MPC computation latency ----
+    def set_latency(self, base, per_iteration=0.0):
+        """the latency between the start of an MPC update and the tick from which the control ticks see its result: base + per_iteration * (IPM
+        iterations of the solve) seconds, each one number or [batch]; the ticks then read the published trajectories (srbm_controller_set_latency).
+        base None removes the setting"""
+        m = self.mpc
+        if base is None:
+            m._chk(self.L.srbm_controller_set_latency(m.h, None))
+            return
+        lat = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(base, float), (m.batch,)),
+                                             np.broadcast_to(np.asarray(per_iteration, float), (m.batch,))], axis=1))
+        m._chk(self.L.srbm_controller_set_latency(m.h, _d(lat)))
+
+    def latency_record(self):
+        """-> pub[batch][8] (LATENCY_RECORD_FIELDS) after the work queued so far"""
+        m = self.mpc
+        pub = np.zeros((m.batch, LATENCY_RECORD_DOUBLES))
+        m._chk(self.L.srbm_controller_get_latency_record(m.h, _d(pub)))
+        return pub
+
+    def published(self, first=0, count=None):
+        """the published trajectories, as BatchMPC.get_trajectory returns the MPC's"""
+        m = self.mpc
+        count = m.batch - first if count is None else count
+        arr = (self.L.Trajectory * count)()          # host.Trajectory, hung on the loaded library by host.lib (this module does not import host.py)
+        m._chk(self.L.srbm_controller_get_published(m.h, int(first), int(count), arr))
+        return arr
+
+    def publish_dev(self, time, update_number, t_start, force=0):
+        """the publish kernel alone on a device pointer (int) time[batch]: update_number = (j - 1) // ticks_per_update of the tick j it precedes,
+        t_start the start of that update, force 1 on a tick an update follows; asynchronous"""
+        self.mpc._chk(self.L.srbm_controller_publish_dev(self.mpc.h, time, int(update_number), float(t_start), int(force)))
 
     # ---- the torque-driven plant ----
     def set_plant(self, kind, kp=None, kd=None, torque_limit=None, substeps=1):

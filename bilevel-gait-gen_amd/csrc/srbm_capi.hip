@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>          // types and prototypes only: RCCL is bound at run time (srbm_allgather_results), the library does not link it
 #include <dlfcn.h>
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include "srbm_wb_ground.hiph"
 #include "srbm_wb_terrain.hiph"
 #include "srbm_contact_feedback.hiph"
+#include "srbm_mpc_latency.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_tick_summary.hiph"
 #include "srbm_batch.hiph"
@@ -127,6 +129,12 @@ struct srbm_batch {
     // contact feedback of the rollout's MPC update (srbm_contact_feedback.hiph)
     int contact_fb = 0;              // 1: the update ticks of srbm_controller_advance run the feedback kernel (srbm_controller_set_contact_feedback)
     double* d_fb = nullptr;          // the feedback record [batch][SRBM_FB_DOUBLES], allocated with d_wb
+    // MPC computation latency of the rollout (srbm_mpc_latency.hiph, srbm_controller_set_latency)
+    SrbmInst* pub_insts = nullptr;   // the published trajectories [batch], what the control tick reads; nullptr: no latency set, it reads insts
+    double* d_lat = nullptr;         // lat[batch][SRBM_LAT_DOUBLES], allocated with pub_insts
+    double* d_pub = nullptr;         // the latency record [batch][SRBM_PUB_DOUBLES], allocated with pub_insts
+    std::vector<double> lat;         // host copy of d_lat (the launches srbm_controller_advance may skip follow from it)
+    std::vector<double> pub_init;    // host image of the record after a reset (the source of the asynchronous copy that resets it)
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -465,6 +473,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_tsum); (void)hipFree(h->d_tsum_ref);
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
+    (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -652,6 +661,12 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     h->terrain_patches = src->terrain_patches;
     if (ok && src->d_terrain)
         ok = hipMalloc(&h->d_terrain, sizeof(double) * WBT_INSTANCE_DOUBLES * B) == hipSuccess && cp(h->d_terrain, src->d_terrain, sizeof(double) * WBT_INSTANCE_DOUBLES * B);
+    // (... and the latency setting with the published trajectories and the latency record)
+    h->lat = src->lat; h->pub_init = src->pub_init;
+    if (ok && src->pub_insts)
+        ok = hipMalloc(&h->pub_insts, sizeof(SrbmInst) * B) == hipSuccess && hipMalloc(&h->d_lat, sizeof(double) * SRBM_LAT_DOUBLES * B) == hipSuccess &&
+             hipMalloc(&h->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * B) == hipSuccess && cp(h->pub_insts, src->pub_insts, sizeof(SrbmInst) * B) &&
+             cp(h->d_lat, src->d_lat, sizeof(double) * SRBM_LAT_DOUBLES * B) && cp(h->d_pub, src->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2179,7 +2194,8 @@ int srbm_control_tick_dev(srbm_batch* h, const double* q_dev, const double* v_de
                           double* q_des_dev, double* v_des_dev, int* contact_dev, double* state_dev, double* ee_dev) {
     if (!h || !q_dev || !v_dev || !time_dev || !control_dev || !qp_sol_dev || !status_dev) return fail("srbm_control_tick: bad arguments");
     if (tick_usable(h) || use_batch(h)) return -1;
-    hipLaunchKernelGGL(srbm_k_tick_targets, dim3(h->batch), dim3(SRBM_TT_THREADS), 0, h->stream, h->dp, h->insts, time_dev, h->d_tick_q, h->d_tick_rec);
+    hipLaunchKernelGGL(srbm_k_tick_targets, dim3(h->batch), dim3(SRBM_TT_THREADS), 0, h->stream, h->dp, h->pub_insts ? h->pub_insts : h->insts, time_dev, h->d_tick_q,
+                       h->d_tick_rec);          // (with a latency set: the published trajectories)
     const SrbmTickIO io{q_dev, v_dev, time_dev, control_dev, qp_sol_dev, status_dev, q_des_dev, v_des_dev, contact_dev, state_dev, ee_dev};
     hipLaunchKernelGGL(srbm_k_tick_control, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wbc, h->d_tick_rec, h->d_tick_q, io);
     HIPCHK(hipGetLastError());
@@ -2216,6 +2232,13 @@ int srbm_control_tick(srbm_batch* h, const double* q, const double* v, const dou
 }
 
 // ---------------- whole-controller rollouts: MPC updates, control ticks, whole-body plant (srbm_wb_plant.hiph) ----------------
+// with a latency set: the published trajectories and the latency record as srbm_controller_set_latency leaves them, on the stream
+static int latency_resync(srbm_batch* h) {
+    if (!h->pub_insts) return 0;
+    HIPCHK(hipMemcpyAsync(h->pub_insts, h->insts, sizeof(SrbmInst) * (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_pub, h->pub_init.data(), sizeof(double) * h->pub_init.size(), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
 int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     if (!h || !q || !v) return fail("srbm_wb_plant_set_state: bad arguments");
     HIPCHK(hipSetDevice(h->device));
@@ -2227,6 +2250,7 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     std::vector<double> fb(SRBM_FB_DOUBLES * (size_t)h->batch);                                                   // no touch-down moved
     for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
+    if (latency_resync(h)) return -1;                                                                             // what is in force: what the MPC holds now
     return srbm_synchronize(h);          // (fb is read until here)
 }
 int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
@@ -2572,6 +2596,119 @@ int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, 
     if (use_batch(h)) return -1;
     return launch_contact_feedback(h, time_dev, cs_dev);
 }
+// ---- MPC computation latency (srbm_mpc_latency.hiph) ----
+static const char* const LAT_NOT_SET = "no latency is set (srbm_controller_set_latency)";
+static int check_latency(const char* fn, int batch, const double* lat) {
+    static const char* const field[SRBM_LAT_DOUBLES] = {"base", "per_iteration"};
+    for (int i = 0; i < batch * SRBM_LAT_DOUBLES; i++)
+        if (!std::isfinite(lat[i]) || lat[i] < 0.0) {
+            char v[64]; std::snprintf(v, sizeof v, "%.17g", lat[i]);
+            return fail(std::string(fn) + ": instance " + std::to_string(i / SRBM_LAT_DOUBLES) + ": " + field[i % SRBM_LAT_DOUBLES] + " is " + v +
+                        " (a finite latency >= 0 in seconds is required)");
+        }
+    return 0;
+}
+int srbm_controller_set_latency(srbm_batch* h, const double* lat) {
+    if (!h) return fail("srbm_controller_set_latency: bad arguments");
+    if (lat && check_latency("srbm_controller_set_latency", h->batch, lat)) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = h->batch;
+    if (!lat) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
+        h->pub_insts = nullptr; h->d_lat = nullptr; h->d_pub = nullptr;
+        h->lat.clear(); h->pub_init.clear();
+        return 0;
+    }
+    if (!h->d_lat) HIPCHK(hipMalloc(&h->d_lat, sizeof(double) * SRBM_LAT_DOUBLES * B));
+    if (!h->d_pub) HIPCHK(hipMalloc(&h->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * B));
+    if (!h->pub_insts) HIPCHK(hipMalloc(&h->pub_insts, sizeof(SrbmInst) * B));          // (last: it is what says that a latency is set)
+    HIPCHK(hipStreamSynchronize(h->stream));                                              // (the host copies below may be the source of a copy under way)
+    h->lat.assign(lat, lat + SRBM_LAT_DOUBLES * B);
+    h->pub_init.assign(SRBM_PUB_DOUBLES * B, 0.0);
+    for (size_t b = 0; b < B; b++) h->pub_init[b * SRBM_PUB_DOUBLES + 3] = -1.0;          // no publication yet
+    HIPCHK(hipMemcpyAsync(h->d_lat, h->lat.data(), sizeof(double) * h->lat.size(), hipMemcpyHostToDevice, h->stream));
+    if (latency_resync(h)) return -1;
+    return srbm_synchronize(h);
+}
+int srbm_controller_get_latency_record(srbm_batch* h, double* pub) {
+    if (!h || !pub) return fail("srbm_controller_get_latency_record: bad arguments");
+    if (!h->pub_insts) return fail(std::string("srbm_controller_get_latency_record: ") + LAT_NOT_SET);
+    return fetch(h, {{pub, h->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * (size_t)h->batch}});
+}
+int srbm_controller_get_published(srbm_batch* h, int first, int count, srbm_trajectory* out) {
+    if (!h || !out || first < 0 || count < 0 || first + count > h->batch) return fail("srbm_controller_get_published: bad arguments");
+    if (!h->pub_insts) return fail(std::string("srbm_controller_get_published: ") + LAT_NOT_SET);
+    std::vector<SrbmInst> v(count);
+    if (fetch(h, {{v.data(), h->pub_insts + first, sizeof(SrbmInst) * (size_t)count}})) return -1;
+    for (int i = 0; i < count; i++) inst_to_record(h->hp, v[i], out + i);
+    return 0;
+}
+static int launch_publish(srbm_batch* h, const double* time, int update_number, double t_start, int force) {
+    hipLaunchKernelGGL(srbm_k_mpc_publish, dim3(h->batch), dim3(SRBM_PUB_THREADS), 0, h->stream, h->insts, h->pub_insts, h->d_lat, time, h->d_pub, update_number,
+                       t_start, force);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_controller_publish_dev(srbm_batch* h, const double* time_dev, int update_number, double t_start, int force) {
+    const std::string fn = "srbm_controller_publish_dev: ";
+    if (!h || !time_dev) return fail(fn + "bad arguments");
+    if (!h->pub_insts) return fail(fn + LAT_NOT_SET);
+    if (update_number < 0 || (force != 0 && force != 1) || !std::isfinite(t_start))
+        return fail(fn + "update_number >= 0, a finite t_start and force 0 or 1 are required");
+    if (use_batch(h)) return -1;
+    return launch_publish(h, time_dev, update_number, t_start, force);
+}
+// The update started after tick k0 = u * ticks_per_update: t_start <- its start (an integer product, then one rounded product); -> the tick before
+// whose targets kernel an instance with {base, per_iteration} whose solve took `iters` iterations is published; *overrun <- 1 if by force.
+// The ticks k0 + 1 .. k0 + ticks_per_update as the kernel sees them, one after the other, through the rule functions the kernel calls.
+static long long latency_publish_tick(long long u, int ticks_per_update, double tick_dt, double base, double per_iteration, int iters, int* overrun) {
+    const long long k0 = u * ticks_per_update;
+    const double t_start = (double)k0 * tick_dt;
+    double L;
+    const double due = srbm_latency_due(t_start, base, per_iteration, iters, &L);
+    for (long long j = k0 + 1; ; j++) {
+        const int what = srbm_latency_decide(0, 1, due, (double)j * tick_dt, j % ticks_per_update == 0);
+        if (what) { if (overrun) *overrun = what == 2; return j; }
+    }
+}
+int srbm_latency_publish_ticks_host(int batch, int first_tick, int ticks, int ticks_per_update, double tick_dt, const double* lat, const int* iters, int n_updates,
+                                    int* publish_tick, int* overrun) {
+    const char* fn = "srbm_latency_publish_ticks_host";
+    if (batch <= 0 || !lat || !iters || n_updates < 0 || !publish_tick || !overrun) return fail(std::string(fn) + ": bad arguments");
+    if (first_tick < 0 || ticks < 0 || ticks > INT_MAX - first_tick) return fail(std::string(fn) + ": first_tick >= 0 and ticks >= 0 are required");
+    if (ticks_per_update < 1) return fail(std::string(fn) + ": ticks_per_update >= 1 is required");
+    if (!std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(std::string(fn) + ": a finite tick_dt > 0 is required");
+    if (check_latency(fn, batch, lat)) return -1;
+    for (int b = 0; b < batch; b++)
+        for (int u = 1; u <= n_updates; u++) {
+            const size_t at = (size_t)b * n_updates + (u - 1);
+            if (iters[at] < 0) return fail(std::string(fn) + ": instance " + std::to_string(b) + ", update " + std::to_string(u) + ": a negative iteration count");
+            int over = 0;
+            const long long j = latency_publish_tick(u, ticks_per_update, tick_dt, lat[b * SRBM_LAT_DOUBLES], lat[b * SRBM_LAT_DOUBLES + 1], iters[at], &over);
+            const bool inside = j >= first_tick && j < (long long)first_tick + ticks;
+            publish_tick[at] = inside ? (int)j : -1;
+            overrun[at] = inside ? over : 0;
+        }
+    return 0;
+}
+// srbm_controller_advance with a latency set: may an instance be published before the targets kernel of tick k?  need[j - k0 - 1] for the ticks
+// k0 + 1 .. k0 + ticks_per_update of update u = k0 / ticks_per_update, from the rule itself: an instance is published no earlier than a solve of no
+// iteration would be and no later than the longest solve would be (the due time grows with the count, rounding included) -- 2 (max_iter + 1) iterations,
+// the two attempts of a solve with a lower start (srbm_k3_ipm.hiph), or the forced tick.  With per_iteration = 0 the two ticks are one.
+// This is the tick for ANY instance pending for update u, whatever older update it holds; an instance whose tick lies before the first tick of a
+// call (a rollout begun there) is due at that first tick, before which controller_advance always launches.
+static void latency_ticks_needed(const srbm_batch* h, long long u, int ticks_per_update, double tick_dt, std::vector<char>& need) {
+    need.assign(ticks_per_update, 0);
+    const long long k0 = u * ticks_per_update;
+    const int most = (int)std::min<long long>(INT_MAX, 2LL * ((long long)h->hp.max_iter + 1));
+    for (int b = 0; b < h->batch; b++) {
+        const double base = h->lat[b * SRBM_LAT_DOUBLES], per = h->lat[b * SRBM_LAT_DOUBLES + 1];
+        const long long lo = latency_publish_tick(u, ticks_per_update, tick_dt, base, per, 0, nullptr);
+        const long long hi = per > 0.0 ? latency_publish_tick(u, ticks_per_update, tick_dt, base, per, most, nullptr) : lo;
+        for (long long j = lo; j <= hi; j++) need[j - k0 - 1] = 1;
+    }
+}
 // MPCController::MPCUpdate's branch on the run number (mpc_controller.cpp:324-346) as srbm_gait_rti_advance has it, on the state, time and ee of
 // the tick (device arrays of the batch), with the record of the run where a step log is enabled
 static int gait_update(srbm_gait* g, int run, int F, const double* state, const double* time, const double* ee) {
@@ -2615,6 +2752,12 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
         return fail(fn + ": the MPC period ticks_per_update * tick_dt is " + v + ": a period below num_nodes * dt = " + std::to_string(horizon) +
                     " is required (beyond it the ticks would read past the trajectory)");
     }
+    // with a latency set a tick can read a trajectory that started up to two periods ago
+    if (h->pub_insts && !(2.0 * period < horizon)) {
+        char v[64]; std::snprintf(v, sizeof v, "%.17g", 2.0 * period);
+        return fail(fn + ": a latency is set (srbm_controller_set_latency) and twice the MPC period, 2 * ticks_per_update * tick_dt, is " + v +
+                    ": below num_nodes * dt = " + std::to_string(horizon) + " is required (a tick can read a trajectory up to two periods old)");
+    }
     // an MPC update follows tick k > 0 with k % ticks_per_update == 0
     auto updates_before = [&](long long k) { return k <= 0 ? 0LL : (k - 1) / ticks_per_update; };          // such k in [0, k)
     const int updates = (int)(updates_before((long long)first_tick + ticks) - updates_before(first_tick));
@@ -2627,9 +2770,21 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
     const size_t B = h->batch;
     const WbBuf w = wb_buf(h);
     hipLaunchKernelGGL(srbm_k_wb_tick_time, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, w.time + (first_tick & 1) * B, h->batch, first_tick, tick_dt);
+    std::vector<char> pub_need;          // with a latency set: the ticks of update pub_need_u before which the publish kernel is launched
+    long long pub_need_u = 0;
     for (int k = first_tick; k < first_tick + ticks; k++) {
         double* const time = w.time + (k & 1) * B;
         const bool update = k > 0 && k % ticks_per_update == 0;
+        // the last update started before tick k is due, or forced, for some instance: its trajectories are published before the tick reads them
+        const long long e = updates_before(k);
+        if (h->pub_insts && e >= 1) {
+            if (e != pub_need_u) { latency_ticks_needed(h, e, ticks_per_update, tick_dt, pub_need); pub_need_u = e; }
+            // (... and before the first tick of every call: pub_need holds for a rollout that has run since update e started.  One begun here on a
+            // state just set has update 0 in force, and whatever the rule would have published before this tick is due now.  In a continued rollout
+            // that launch finds nobody both pending and due and touches nothing.)
+            if ((k == first_tick || pub_need[k - e * ticks_per_update - 1]) &&
+                launch_publish(h, time, (int)e, (double)(e * ticks_per_update) * tick_dt, update ? 1 : 0)) return -1;
+        }
         if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
         // mpc_controller.cpp:322: the contacts measured at t_k -- the ground's state after tick k - 1 -- re-time the plan the update starts from
         if (update && h->contact_fb && launch_contact_feedback(h, time, h->d_cs)) return -1;

@@ -262,6 +262,11 @@ int srbm_controller_set_contact_feedback(srbm_batch*, int)
 int srbm_controller_get_contact_feedback(srbm_batch*, double*)
 int srbm_controller_contact_feedback_dev(srbm_batch*, dev*, dev*)
 int srbm_gait_controller_advance(srbm_gait*, int, int, int, double, int)
+int srbm_controller_set_latency(srbm_batch*, double*)
+int srbm_controller_get_latency_record(srbm_batch*, double*)
+int srbm_controller_get_published(srbm_batch*, int, int, srbm_trajectory*)
+int srbm_controller_publish_dev(srbm_batch*, dev*, int, double, int)
+int srbm_latency_publish_ticks_host(int, int, int, int, double, double*, int*, int, int*, int*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)
@@ -334,6 +339,7 @@ def lib(large=False):
         cap = (C.c_int * 4)()
         L.srbm_get_capacity(cap)
         L.capacity = dict(N=cap[0], nu=cap[1], samples=cap[2], knots=cap[3])
+        L.Trajectory = Trajectory          # the record type, for the modules beside this one that do not import it (controller_rollout.published)
         _libs[path] = L
     return _libs[path]
 

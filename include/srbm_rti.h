@@ -546,7 +546,8 @@ int srbm_wb_plant_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_de
  *   2. the plant step, and the record of the tick if a tick log is enabled;
  *   3. if k > 0 and k % ticks_per_update == 0: srbm_get_real_time_update_dev on the state and ee that step 1 wrote, at init_time = t_k.  The new
  *      trajectories are in force from tick k + 1 on: ComputeControlAction publishes (mpc_controller.cpp:142-156), the MPC thread picks up, with zero
- *      computation delay.  With a step log enabled that solve writes its usual record, so srbm_rollout_summary_fold works on such a rollout unchanged.
+ *      computation delay -- unless a latency is set (srbm_controller_set_latency, below: the ticks then read the PUBLISHED trajectories, which follow
+ *      the MPC's by the latency of each instance).  With a step log enabled that solve writes its usual record, so srbm_rollout_summary_fold works on such a rollout unchanged.
  * The MPC period ticks_per_update * tick_dt is batch-wide and may lie off the node grid (as srbm_plant_set_period established).
  * Refused with a message, nothing launched, plant, trajectories, q_des and both log cursors untouched: no plant state set; no leg kinematics; no
  * whole-body model; no srbm_control_tick_reset; first_tick < 0; ticks < 0; ticks_per_update < 1; tick_dt not finite or <= 0;
@@ -883,6 +884,80 @@ int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, 
  * entry is bitwise srbm_controller_advance.  Refused in addition: a NULL handle, gait_opt_freq <= 0.  The caller's own srbm_gait_compute_gradient /
  * _sensitivity after a rollout still refuse a last solve that ended by the step rule. */
 int srbm_gait_controller_advance(srbm_gait* g, int first_tick, int ticks, int ticks_per_update, double tick_dt, int gait_opt_freq);
+
+/* ---- MPC computation latency: the time between the start of an MPC update and the tick from which the control tick sees its result ----
+ * The reference's MPC thread (controllers/mpc_controller.cpp:299-398) loops: newest state sample, solve, publish traj_, again; ComputeControlAction
+ * (:120-227) evaluates the old traj_ while the solve runs, so every trajectory comes into force one solve late.  A setting of the batch, off by
+ * default; with it off every entry is byte for byte what it is without this section.
+ *
+ * lat[batch][2] = {base, per_iteration}, seconds, finite and >= 0.  With a latency set the batch holds a second set of instance records, the
+ * PUBLISHED trajectories, and srbm_control_tick[_dev] -- hence the ticks of srbm_controller_advance and srbm_gait_controller_advance -- read those.
+ * Every other entry (srbm_get_trajectory, srbm_eval_trajectory, the step log, contact feedback, the updates) keeps working on the MPC's records.
+ *
+ * The rule.  The update that follows tick k (k > 0, k % ticks_per_update == 0) is update number u = k / ticks_per_update; it starts at
+ *     t_start = (u * ticks_per_update) * tick_dt          an integer product, then one rounded product, as t_k everywhere
+ * and for instance b, whose record holds qp_iters after that update (in a gait run: the installed winner's count), every rounded operation a
+ * statement of its own,
+ *     p   = per_iteration * qp_iters
+ *     L   = base + p
+ *     due = t_start + L
+ * Before the targets kernel of tick j >= 1 let e = (j - 1) / ticks_per_update (integer division): the number of the last update started before
+ * tick j, 0 for none.  Instance b is PENDING while the update number of its published record is below e.  A pending instance is published -- its
+ * whole record copied from the MPC's set to the published set -- if
+ *     due <= time[b]                                       time: the tick's own time array, t_j
+ *  or the tick is forced: j % ticks_per_update == 0 and e >= 1.
+ * The forced tick is the reference's thread structure: a solve cannot start before the last one was handed over, so the effective latency is
+ * min(L, period); a forced publication with due > time[b] is counted as an overrun.  L = 0 everywhere is the behaviour without the setting (in
+ * force from tick k + 1); base = ticks_per_update * tick_dt is the reference's thread, solves back to back, each in force one solve late;
+ * per_iteration > 0 makes the latency follow the work of the solve, decided on the device without synchronisation.  The state is the published
+ * update number of each instance and e follows from j: a rollout cut anywhere and continued is the same rollout.  (A rollout BEGUN at a later tick on
+ * a state just set finds update number 0 in force and e > 0: its first ticks publish the trajectories found, the same bytes, as update e.)
+ * What the setting is NOT: the MPC period stays batch-wide and fixed -- a latency beyond it is capped and counted, not turned into a slower MPC
+ * rate; no model of the control tick's own computation time; no jitter.
+ *
+ * The latency record pub[batch][8]:
+ *     0    update number in force (0: the trajectories found when the latency or the plant's state was set)
+ *     1    publications
+ *     2    overruns
+ *     3    time of the last publication (-1: none)
+ *     4    t_start of the trajectory in force (0 before the first publication)
+ *     5    L of the last publication as computed
+ *     6    max L over the publications
+ *     7    sum of time - t_start over the publications, in publication order
+ *
+ * srbm_controller_set_latency: NULL removes the setting and frees the published set; otherwise allocates the set and fills it and the record from
+ * the MPC's records as they are after the work queued so far.  Refused, naming the instance and the field, the batch untouched, for a value that is
+ * not finite or negative.  srbm_wb_plant_set_state re-synchronises the published set with the MPC's and resets the record; srbm_batch_clone carries
+ * the setting, the published set and the record.  An entry that replaces the MPC's trajectories from outside (srbm_set_warm_start_trajectory,
+ * srbm_create_initial_run) does not touch the published set: set the latency, or the plant's state, after it.
+ * srbm_controller_get_latency_record: pub[batch][8] after the work queued so far.  srbm_controller_get_published: srbm_get_trajectory on the
+ * published set.  Both refused without a latency set.
+ * srbm_controller_publish_dev: the publish kernel alone (csrc/srbm_mpc_latency.hiph) on the caller's time_dev[batch], for tests and host-driven
+ * chains: update_number is e, t_start and force as above.  One launch on the batch's stream, no copy, no synchronisation; an instance that is not
+ * published is not touched, record included.  Refused without a latency set, for update_number < 0, a t_start that is not finite, force not 0 / 1.
+ *
+ * In srbm_controller_advance and srbm_gait_controller_advance with a latency set the kernel runs before srbm_control_tick_dev of tick j, on the
+ * tick's time array; contact feedback, the plant and the update are untouched (contact feedback edits the MPC's records, as
+ * AdjustForCurrentContacts does in the reference's MPC thread).  The launch is skipped on the ticks on which the rule itself proves that no
+ * instance is published: before the tick on which a solve of no iteration would be due, and after the tick on which the longest solve the solver
+ * settings allow, or the forced tick, publishes -- with per_iteration = 0 that leaves the instance's one publication tick.  Before the FIRST tick of
+ * every call (with e >= 1) the kernel is always launched: those ticks are computed for a rollout that has run since the update started, and in a
+ * rollout begun at this tick on a state just set whatever the rule would have published earlier is due now; in a continued rollout that launch finds
+ * nobody both pending and due.  Skipping changes no byte: the entry in one call, in one call per tick and the host-driven chain that launches
+ * srbm_controller_publish_dev before every tick leave the same bytes, the latency record included, from tick 0 and from a later tick.
+ * A tick can then read a trajectory up to two periods old: refused in addition, with both numbers in the message and nothing launched,
+ * 2 * ticks_per_update * tick_dt >= num_nodes * dt.
+ *
+ * srbm_latency_publish_ticks_host needs no GPU: for a rollout from tick 0, lat[batch][2] and iters[batch][n_updates], iters[b][u - 1] the
+ * iteration count of update u of instance b, publish_tick[batch][n_updates] <- the tick before whose targets kernel update u of instance b is
+ * published and overrun[batch][n_updates] <- 1 if by force before it was due -- for the publications that fall among the ticks
+ * first_tick .. first_tick + ticks - 1; -1 and 0 for the others.  The same rule functions as the kernel's. */
+int srbm_controller_set_latency(srbm_batch* h, const double* lat);
+int srbm_controller_get_latency_record(srbm_batch* h, double* pub);
+int srbm_controller_get_published(srbm_batch* h, int first, int count, srbm_trajectory* out);
+int srbm_controller_publish_dev(srbm_batch* h, const double* time_dev, int update_number, double t_start, int force);
+int srbm_latency_publish_ticks_host(int batch, int first_tick, int ticks, int ticks_per_update, double tick_dt, const double* lat, const int* iters, int n_updates,
+                                    int* publish_tick, int* overrun);
 
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */

@@ -18,6 +18,14 @@ medians and spreads.
                  what the feedback costs -- per update: the difference times ticks_per_update
   (g) gait       (e) at S = 4 through srbm_gait_controller_advance with gait_opt_freq 5, feedback off, 250 ticks so that the updates are three plain
                  ones, one with gradient and LP (run 4) and one line search (run 5); ms per tick over those 250 ticks
+  (l) latency    (a) logged with an MPC computation latency set (srbm_controller_set_latency): 0 everywhere; a constant 20 ms (one launch of the
+                 publish kernel per update); per_iteration 1 ms with base 0 (the kernel launched before every tick of a period: nothing bounds
+                 the solve's iterations below the forced tick); each beside (a) logged of the same run, with the
+                 iterations of the whole-body QP per tick and of the IPM per update (a step log is on): trajectories in force later make other
+                 rollouts, whose ticks and updates cost what their solves take.  And the publish kernel alone
+                 (srbm_controller_publish_dev), 200 launches in which every instance is published (a new update number each, forced) and 200 in
+                 which none is (the same update number again); and (b) with latency 0 set and the publish kernel launched before every tick: the same
+                 rollout as (b), so the difference is what a launch per tick costs.  Skipped, with a note, on a library without the setting
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -56,6 +64,9 @@ def main():
            'ground_s1_logged': [], 'ground_s4_logged': [], 'ground_step_s1': [], 'ground_step_s4': [], 'ground_s4_feedback_logged': [],
            'ground_s4_gait_f5_logged': []}
     has_terrain = hasattr(ControllerRollout, 'set_terrain')
+    has_latency = hasattr(ControllerRollout, 'set_latency')
+    if has_latency:
+        res.update({'latency_0': [], 'latency_20ms': [], 'latency_per_iteration': [], 'chain_latency_0_every_tick': [], 'publish_all': [], 'publish_none': []})
     if has_terrain:
         res.update({'terrain_s4_logged': [], 'terrain_step_s1': [], 'terrain_step_s4': []})
     ground = terrain = None
@@ -90,6 +101,8 @@ def main():
                 info['coasted_ticks'] = int(((log[:, :, F['flags']].astype(int) & FLAG_COAST) != 0).sum())
                 info['targets_not_ok'] = int((log[:, :, F['targets_status']] != 0).sum())
                 info['base_height_range'] = [float(log[:, :, 8].min()), float(log[:, :, 8].max())]
+                info['mean_qp_iterations'] = float(log[:, :, F['qp_iters']].mean())
+                info['slowest_qp_iterations_mean'] = float(log[:, :, F['qp_iters']].max(axis=1).mean())
             info['finite_' + name] = bool(np.all(np.isfinite(R.state()[0])))
         # (d) the torque-driven plant
         for S in (1, 4):
@@ -189,6 +202,21 @@ def main():
                                                 ready_after_the_gradient_run=int(steps[:, :, 59].max(axis=0).sum()),
                                                 searched_in_the_line_search=int((steps[:, :, 58] == 2).sum()))
         gait.close()
+        # (l) the logged entry with a latency set
+        for name, lat in (('latency_0', (0.0, 0.0)), ('latency_20ms', (0.02, 0.0)), ('latency_per_iteration', (0.0, 1e-3))) if has_latency else ():
+            g, R = fresh(TICKS + 3)
+            R.set_latency(*lat)
+            g.step_log_enable(TICKS // TPU + 1)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            rec, log, steps = R.latency_record(), R.tick_log(), g.step_log()
+            info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), mean_qp_iterations=float(log[:, :, F['qp_iters']].mean()),
+                              slowest_qp_iterations_mean=float(log[:, :, F['qp_iters']].max(axis=1).mean()),
+                              updates=int(steps.shape[0]), mean_ipm_iterations=float(steps[:, :, 11].mean()),
+                              slowest_ipm_iterations_mean=float(steps[:, :, 11].max(axis=1).mean()), publications=int(rec[:, 1].sum()), overruns=int(rec[:, 2].sum()),
+                              max_latency=float(rec[:, 6].max()), mean_age_at_publication=float((rec[:, 7] / np.maximum(rec[:, 1], 1)).mean()))
         # (b) the same loop from the host, on torch's buffers, on the batch's stream
         g, R = fresh()
         T = ControlTick(g)
@@ -254,10 +282,57 @@ def main():
                     signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
                     res['terrain_step_s%d' % S].append(timed(g, ground_step))
                     R.set_terrain(None)
+            # ... and the publish kernel alone: every instance published, no instance published
+            if has_latency:
+                R.set_latency(0.0)
+                counter = [0]
+
+                def publish_all():
+                    for k in range(TICKS):
+                        counter[0] += 1
+                        R.publish_dev(t_d.data_ptr(), counter[0], 0.0, 1)
+
+                def publish_none():
+                    for k in range(TICKS):
+                        R.publish_dev(t_d.data_ptr(), counter[0], 0.0, 1)
+                for name, fn in (('publish_all', publish_all), ('publish_none', publish_none)):
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    fn()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    res[name].append(timed(g, fn))
+                info['publish_all_publications'] = int(R.latency_record()[:, 1].sum())
+                R.set_latency(None)
+        # ... and what a launch before EVERY tick costs in a rollout that is otherwise (b): the chain with latency 0 set, the publish kernel launched before
+        # every tick (it publishes before the tick after an update and returns on its decision before every other one)
+        if has_latency:
+            g, R = fresh()
+            R.set_latency(0.0)
+            T = ControlTick(g)
+            with torch.cuda.stream(torch.cuda.ExternalStream(g.stream())):
+                q_d, v_d, t_d = torch.tensor(q0, **f64), torch.tensor(v0, **f64), torch.zeros(B, **f64)
+                ctl_d, sol_d, x_d, ee_d = torch.zeros((B, 36), **f64), torch.zeros((B, 30), **f64), torch.zeros((B, 13), **f64), torch.zeros((B, 12), **f64)
+                st_d, con_d = torch.zeros((B, 2), dtype=torch.int32, device='cuda'), torch.zeros((B, 4), dtype=torch.int32, device='cuda')
+
+                def chain_published(first, n):
+                    for k in range(first, first + n):
+                        signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                        t_d.fill_(k * DT)
+                        e = (k - 1) // TPU if k >= 1 else 0
+                        R.publish_dev(t_d.data_ptr(), e, (e * TPU) * DT, int(k % TPU == 0 and e >= 1))
+                        T.tick_dev(q_d.data_ptr(), v_d.data_ptr(), t_d.data_ptr(), ctl_d.data_ptr(), sol_d.data_ptr(), st_d.data_ptr(), None, None,
+                                   con_d.data_ptr(), x_d.data_ptr(), ee_d.data_ptr())
+                        R.plant_step_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), sol_d.data_ptr(), st_d.data_ptr())
+                        if k > 0 and k % TPU == 0:
+                            g.get_real_time_update_dev(x_d.data_ptr(), t_d.data_ptr(), ee_d.data_ptr())
+                chain_published(0, 3)
+                res['chain_latency_0_every_tick'].append(timed(g, lambda: chain_published(3, TICKS)))
+                info['chain_latency_0_publications'] = int(R.latency_record()[:, 1].sum())
     signal.setitimer(signal.ITIMER_REAL, 0)
     med = {k: float(np.median(v)) for k, v in res.items()}
     if not has_terrain:
         info['terrain'] = 'this library has no terrain: rows (t) skipped'
+    if not has_latency:
+        info['latency'] = 'this library has no latency setting: rows (l) skipped'
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
                           spread_ms={k: float(max(v) - min(v)) for k, v in res.items()}, **info)))
 
