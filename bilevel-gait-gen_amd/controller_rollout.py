@@ -23,7 +23,9 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.advance(0, 200, 50, 1e-3, gait=go, gait_opt_freq=5)      the same with the gait step of host.BatchGaitOptimizer `go` in the updates
     R.set_latency(0.02)                   optional: every update comes into force 20 ms after it started, not at the next tick; per instance:
                                           R.set_latency(base[batch], per_iteration) -- base + per_iteration * (IPM iterations of the solve)
-    q, v = R.state(); log = R.tick_log(); pub = R.latency_record()"""
+    R.set_sensors(sens, seed)             optional: the ticks read a measurement of (q, v) -- mocap rate and delay, noise, gyro bias, low-pass filters --
+                                          sens[batch][16] from srbm_loader.sensors.record(...), one 64-bit seed per instance
+    q, v = R.state(); log = R.tick_log(); pub = R.latency_record(); qm, vm = R.measured(); srec = R.sensor_record()"""
 import ctypes as C
 
 import numpy as np
@@ -49,6 +51,10 @@ LATENCY_RECORD_DOUBLES = 8          # the latency record of an instance (set_lat
 LATENCY_RECORD_FIELDS = dict(update_in_force=0, publications=1, overruns=2, last_publication_time=3, t_start_in_force=4, last_latency=5, max_latency=6,
                              age_sum=7)
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
+_llp = C.POINTER(C.c_longlong)
+SENSOR_DOUBLES, SENSOR_STATE_DOUBLES, SENSOR_RECORD_DOUBLES = 16, 72, 8          # set_sensors: the setting, the state and the record of an instance
+SENSOR_RECORD_FIELDS = dict(ticks=0, samples=1, max_position=2, max_orientation=3, max_linear_velocity=4, max_angular_velocity=5, max_joint_angle=6,
+                            max_joint_rate=7)
 
 
 def _d(a):
@@ -180,6 +186,58 @@ class ControllerRollout:
         """the publish kernel alone on a device pointer (int) time[batch]: update_number = (j - 1) // ticks_per_update of the tick j it precedes,
         t_start the start of that update, force 1 on a tick an update follows; asynchronous"""
         self.mpc._chk(self.L.srbm_controller_publish_dev(self.mpc.h, time, int(update_number), float(t_start), int(force)))
+
+    # ---- sensor model ----
+    def set_sensors(self, sens, seed=0):
+        """the ticks read a measurement of the plant's (q, v) (srbm_controller_set_sensors): sens one [16] or [batch][16] (sensors.record builds one
+        from physical values), seed one integer or [batch], 64 bits each.  sens None removes the setting"""
+        m = self.mpc
+        if sens is None:
+            m._chk(self.L.srbm_controller_set_sensors(m.h, None, None))
+            return
+        sens = np.ascontiguousarray(np.broadcast_to(np.asarray(sens, float), (m.batch, SENSOR_DOUBLES)))
+        seed = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (m.batch,))).view(np.int64)
+        m._chk(self.L.srbm_controller_set_sensors(m.h, _d(sens), seed.ctypes.data_as(_llp)))
+
+    def sensors(self):
+        """-> sens[batch][16], seed[batch] (uint64) as set"""
+        m = self.mpc
+        sens, seed = np.zeros((m.batch, SENSOR_DOUBLES)), np.zeros(m.batch, np.int64)
+        m._chk(self.L.srbm_controller_get_sensors(m.h, _d(sens), seed.ctypes.data_as(_llp)))
+        return sens, seed.view(np.uint64)
+
+    def sensor_state(self):
+        """-> ms[batch][72]: the pose ring, the sample count and the filter memories (the table in include/srbm_rti.h) after the work queued so far"""
+        m = self.mpc
+        ms = np.zeros((m.batch, SENSOR_STATE_DOUBLES))
+        m._chk(self.L.srbm_controller_get_sensor_state(m.h, _d(ms)))
+        return ms
+
+    def set_sensor_state(self, ms):
+        m = self.mpc
+        ms = np.ascontiguousarray(ms, float)
+        if ms.shape != (m.batch, SENSOR_STATE_DOUBLES):
+            raise ValueError('ms is [batch][%d]' % SENSOR_STATE_DOUBLES)
+        m._chk(self.L.srbm_controller_set_sensor_state(m.h, _d(ms)))
+
+    def sensor_record(self):
+        """-> srec[batch][8] (SENSOR_RECORD_FIELDS) after the work queued so far"""
+        m = self.mpc
+        srec = np.zeros((m.batch, SENSOR_RECORD_DOUBLES))
+        m._chk(self.L.srbm_controller_get_sensor_record(m.h, _d(srec)))
+        return srec
+
+    def measured(self):
+        """-> qm[batch][19], vm[batch][18]: what the last tick read"""
+        m = self.mpc
+        q, v = np.zeros((m.batch, 19)), np.zeros((m.batch, 18))
+        m._chk(self.L.srbm_controller_get_measured(m.h, _d(q), _d(v)))
+        return q, v
+
+    def measure_dev(self, tick, tick_dt, q, v, qm, vm):
+        """the measure kernel alone on device pointers (ints): the true q[batch][19], v[batch][18] -> qm, vm; moves the batch's sensor state and record by
+        tick `tick`; asynchronous"""
+        self.mpc._chk(self.L.srbm_controller_measure_dev(self.mpc.h, int(tick), float(tick_dt), q, v, qm, vm))
 
     # ---- the torque-driven plant ----
     def set_plant(self, kind, kp=None, kd=None, torque_limit=None, substeps=1):

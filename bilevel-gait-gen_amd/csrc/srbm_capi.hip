@@ -27,6 +27,7 @@
 #include "srbm_wb_terrain.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_mpc_latency.hiph"
+#include "srbm_sensors.hiph"
 #include "srbm_rollout_summary.hiph"
 #include "srbm_tick_summary.hiph"
 #include "srbm_batch.hiph"
@@ -135,6 +136,11 @@ struct srbm_batch {
     double* d_pub = nullptr;         // the latency record [batch][SRBM_PUB_DOUBLES], allocated with pub_insts
     std::vector<double> lat;         // host copy of d_lat (the launches srbm_controller_advance may skip follow from it)
     std::vector<double> pub_init;    // host image of the record after a reset (the source of the asynchronous copy that resets it)
+    // sensor model of the rollout (srbm_sensors.hiph, srbm_controller_set_sensors): one allocation d_sens, nullptr: no sensors set, the ticks read the plant
+    double* d_sens = nullptr;        // [batch] x {record SRBM_SENS_DEV_DOUBLES, state, record of the run, qm[19], vm[18]}: sens_buf(); then seed[batch]
+    bool sens_ready = false;         // the sensor state was initialised from a plant state
+    std::vector<double> sens;        // host copy of the caller's sens[batch][SRBM_SENS_DOUBLES]
+    std::vector<unsigned long long> sens_seed;
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -474,6 +480,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
+    (void)hipFree(h->d_sens);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -497,6 +504,18 @@ static WbBuf wb_buf(const srbm_batch* h) {
     w.ee = w.state + 13 * B;
     w.status = h->d_wb_int; w.contact = w.status + 2 * B;
     return w;
+}
+// the buffers of the sensor model, one allocation: per instance the device copy of the record, the state, the record of the run and the last
+// measurement (qm, vm), then the seeds
+struct SensBuf { double *S, *ms, *srec, *qm, *vm; unsigned long long* seed; };
+enum { SENS_BUF_DOUBLES = SRBM_SENS_DEV_DOUBLES + SRBM_SENS_STATE_DOUBLES + SRBM_SENS_RECORD_DOUBLES + 19 + 18 };
+static size_t sens_bytes(size_t B) { return sizeof(double) * SENS_BUF_DOUBLES * B + sizeof(unsigned long long) * B; }
+static SensBuf sens_buf(const srbm_batch* h) {
+    const size_t B = h->batch;
+    SensBuf s;
+    s.S = h->d_sens; s.ms = s.S + SRBM_SENS_DEV_DOUBLES * B; s.srec = s.ms + SRBM_SENS_STATE_DOUBLES * B; s.qm = s.srec + SRBM_SENS_RECORD_DOUBLES * B;
+    s.vm = s.qm + 19 * B; s.seed = reinterpret_cast<unsigned long long*>(s.vm + 18 * B);
+    return s;
 }
 static int wb_alloc(srbm_batch* h) {
     const size_t B = h->batch;
@@ -667,6 +686,9 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
         ok = hipMalloc(&h->pub_insts, sizeof(SrbmInst) * B) == hipSuccess && hipMalloc(&h->d_lat, sizeof(double) * SRBM_LAT_DOUBLES * B) == hipSuccess &&
              hipMalloc(&h->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * B) == hipSuccess && cp(h->pub_insts, src->pub_insts, sizeof(SrbmInst) * B) &&
              cp(h->d_lat, src->d_lat, sizeof(double) * SRBM_LAT_DOUBLES * B) && cp(h->d_pub, src->d_pub, sizeof(double) * SRBM_PUB_DOUBLES * B);
+    // (... and the sensor setting with the sensor state, its record and the last measurement)
+    h->sens = src->sens; h->sens_seed = src->sens_seed; h->sens_ready = src->sens_ready;
+    if (ok && src->d_sens) ok = hipMalloc(&h->d_sens, sens_bytes(B)) == hipSuccess && cp(h->d_sens, src->d_sens, sens_bytes(B));
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2239,6 +2261,21 @@ static int latency_resync(srbm_batch* h) {
     HIPCHK(hipMemcpyAsync(h->d_pub, h->pub_init.data(), sizeof(double) * h->pub_init.size(), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
+// with sensors set: the sensor state of a plant at (q, v) (host arrays), the record of the run zeroed, the last measurement (q, v); synchronous
+static int sensors_reinit(srbm_batch* h, const double* q, const double* v) {
+    if (!h->d_sens) return 0;
+    const size_t B = h->batch;
+    const SensBuf s = sens_buf(h);
+    std::vector<double> ms(SRBM_SENS_STATE_DOUBLES * B);
+    for (size_t b = 0; b < B; b++) srbm_sensor_state_init(q + 19 * b, v + 18 * b, ms.data() + SRBM_SENS_STATE_DOUBLES * b);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(s.ms, ms.data(), sizeof(double) * ms.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(s.srec, 0, sizeof(double) * SRBM_SENS_RECORD_DOUBLES * B));
+    HIPCHK(hipMemcpy(s.qm, q, sizeof(double) * 19 * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.vm, v, sizeof(double) * 18 * B, hipMemcpyHostToDevice));
+    h->sens_ready = true;
+    return 0;
+}
 int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     if (!h || !q || !v) return fail("srbm_wb_plant_set_state: bad arguments");
     HIPCHK(hipSetDevice(h->device));
@@ -2251,7 +2288,8 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
     if (latency_resync(h)) return -1;                                                                             // what is in force: what the MPC holds now
-    return srbm_synchronize(h);          // (fb is read until here)
+    if (srbm_synchronize(h)) return -1;          // (fb is read until here)
+    return sensors_reinit(h, q, v);
 }
 int srbm_wb_plant_get_state(srbm_batch* h, double* q, double* v) {
     if (!h) return fail("srbm_wb_plant_get_state: bad arguments");
@@ -2709,6 +2747,148 @@ static void latency_ticks_needed(const srbm_batch* h, long long u, int ticks_per
         for (long long j = lo; j <= hi; j++) need[j - k0 - 1] = 1;
     }
 }
+// ---- sensor model (srbm_sensors.hiph) ----
+static const char* const SENS_NOT_SET = "no sensors are set (srbm_controller_set_sensors)";
+static const char* const SENS_NO_STATE = "sensors are set but the plant's state is not (srbm_wb_plant_set_state): the sensor state starts from it";
+static int check_sensors(const char* fn, int batch, const double* sens) {
+    static const char* const field[SRBM_SENS_DOUBLES] = {"mocap_ticks", "mocap_delay", "sigma_p", "sigma_r", "velocity_source", "sigma_v", "sigma_w", "gyro_bias[0]",
+                                                         "gyro_bias[1]", "gyro_bias[2]", "sigma_qj", "sigma_vj", "lpf_x_base", "lpf_x_joints", "reserved[14]",
+                                                         "reserved[15]"};
+    for (int i = 0; i < batch * SRBM_SENS_DOUBLES; i++) {
+        const int f = i % SRBM_SENS_DOUBLES;
+        const double x = sens[i];
+        const char* need = nullptr;
+        if (!std::isfinite(x)) need = "a finite value";
+        else if (f == 0 && !(x == std::floor(x) && x >= 1.0 && x <= 64.0)) need = "an integer 1..64";
+        else if (f == 1 && !(x == std::floor(x) && x >= 0.0 && x <= 3.0)) need = "an integer 0..3";
+        else if (f == 4 && !(x == 0.0 || x == 1.0)) need = "0 (the plant's) or 1 (the finite difference)";
+        else if (f >= 14 && x != 0.0) need = "0";
+        else if (!(f >= 7 && f <= 9) && x < 0.0) need = "a value >= 0";
+        if (need) {
+            char v[64]; std::snprintf(v, sizeof v, "%.17g", x);
+            return fail(std::string(fn) + ": instance " + std::to_string(i / SRBM_SENS_DOUBLES) + ": " + field[f] + " is " + v + " (" + need + " is required)");
+        }
+    }
+    return 0;
+}
+int srbm_controller_set_sensors(srbm_batch* h, const double* sens, const long long* seed) {
+    const char* fn = "srbm_controller_set_sensors";
+    if (!h || (sens && !seed)) return fail(std::string(fn) + ": bad arguments");
+    if (sens && check_sensors(fn, h->batch, sens)) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t B = h->batch;
+    if (!sens) {
+        (void)hipFree(h->d_sens);
+        h->d_sens = nullptr; h->sens_ready = false;
+        h->sens.clear(); h->sens_seed.clear();
+        return 0;
+    }
+    if (!h->d_sens) {
+        HIPCHK(hipMalloc(&h->d_sens, sens_bytes(B)));
+        HIPCHK(hipMemset(h->d_sens, 0, sens_bytes(B)));
+        h->sens_ready = false;
+    }
+    h->sens.assign(sens, sens + SRBM_SENS_DOUBLES * B);
+    h->sens_seed.resize(B);
+    for (size_t b = 0; b < B; b++) h->sens_seed[b] = (unsigned long long)seed[b];
+    std::vector<double> S(SRBM_SENS_DEV_DOUBLES * B);
+    for (size_t b = 0; b < B; b++) srbm_sensor_device_record(sens + SRBM_SENS_DOUBLES * b, S.data() + SRBM_SENS_DEV_DOUBLES * b);
+    const SensBuf s = sens_buf(h);
+    HIPCHK(hipMemcpy(s.S, S.data(), sizeof(double) * S.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.seed, h->sens_seed.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice));
+    if (!h->d_wb) return 0;          // (srbm_wb_plant_set_state will start the sensor state)
+    // the sensor state starts from the plant's state as it is after the work queued so far
+    std::vector<double> q(19 * B), v(18 * B);
+    const WbBuf w = wb_buf(h);
+    if (copy_each({{q.data(), w.q, sizeof(double) * q.size()}, {v.data(), w.v, sizeof(double) * v.size()}}, hipMemcpyDeviceToHost)) return -1;
+    return sensors_reinit(h, q.data(), v.data());
+}
+int srbm_controller_get_sensors(srbm_batch* h, double* sens, long long* seed) {
+    if (!h || !sens || !seed) return fail("srbm_controller_get_sensors: bad arguments");
+    if (!h->d_sens) return fail(std::string("srbm_controller_get_sensors: ") + SENS_NOT_SET);
+    std::memcpy(sens, h->sens.data(), sizeof(double) * h->sens.size());
+    for (size_t b = 0; b < h->sens_seed.size(); b++) seed[b] = (long long)h->sens_seed[b];
+    return 0;
+}
+int srbm_controller_get_sensor_state(srbm_batch* h, double* ms) {
+    if (!h || !ms) return fail("srbm_controller_get_sensor_state: bad arguments");
+    if (!h->d_sens) return fail(std::string("srbm_controller_get_sensor_state: ") + SENS_NOT_SET);
+    if (!h->sens_ready) return fail(std::string("srbm_controller_get_sensor_state: ") + SENS_NO_STATE);
+    return fetch(h, {{ms, sens_buf(h).ms, sizeof(double) * SRBM_SENS_STATE_DOUBLES * (size_t)h->batch}});
+}
+int srbm_controller_set_sensor_state(srbm_batch* h, const double* ms) {
+    const std::string fn = "srbm_controller_set_sensor_state: ";
+    if (!h || !ms) return fail(fn + "bad arguments");
+    if (!h->d_sens) return fail(fn + SENS_NOT_SET);
+    for (int b = 0; b < h->batch; b++) {
+        const double n = ms[(size_t)b * SRBM_SENS_STATE_DOUBLES];
+        if (!(std::isfinite(n) && n == std::floor(n) && n >= 0.0 && n <= 4503599627370496.0))
+            return fail(fn + "instance " + std::to_string(b) + ": the sample count (entry 0) must be an integer 0 .. 2^52");
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(sens_buf(h).ms, ms, sizeof(double) * SRBM_SENS_STATE_DOUBLES * (size_t)h->batch, hipMemcpyHostToDevice));
+    h->sens_ready = true;
+    return 0;
+}
+int srbm_controller_get_sensor_record(srbm_batch* h, double* srec) {
+    if (!h || !srec) return fail("srbm_controller_get_sensor_record: bad arguments");
+    if (!h->d_sens) return fail(std::string("srbm_controller_get_sensor_record: ") + SENS_NOT_SET);
+    return fetch(h, {{srec, sens_buf(h).srec, sizeof(double) * SRBM_SENS_RECORD_DOUBLES * (size_t)h->batch}});
+}
+int srbm_controller_get_measured(srbm_batch* h, double* q, double* v) {
+    if (!h) return fail("srbm_controller_get_measured: bad arguments");
+    if (!h->d_sens) return fail(std::string("srbm_controller_get_measured: ") + SENS_NOT_SET);
+    const SensBuf s = sens_buf(h);
+    return fetch(h, {{q, s.qm, sizeof(double) * 19 * (size_t)h->batch}, {v, s.vm, sizeof(double) * 18 * (size_t)h->batch}});
+}
+static int launch_measure(srbm_batch* h, int tick, double tick_dt, const double* q, const double* v, double* qm, double* vm) {
+    const SensBuf s = sens_buf(h);
+    hipLaunchKernelGGL(srbm_k_measure, dim3(h->batch), dim3(64), 0, h->stream, s.S, s.seed, tick, tick_dt, q, v, s.ms, s.srec, qm, vm);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_controller_measure_dev(srbm_batch* h, int tick, double tick_dt, const double* q_dev, const double* v_dev, double* qm_dev, double* vm_dev) {
+    const std::string fn = "srbm_controller_measure_dev: ";
+    if (!h || !q_dev || !v_dev || !qm_dev || !vm_dev) return fail(fn + "bad arguments");
+    if (!h->d_sens) return fail(fn + SENS_NOT_SET);
+    if (!h->sens_ready) return fail(fn + SENS_NO_STATE);
+    if (q_dev == qm_dev || v_dev == vm_dev) return fail(fn + "the measurement must not be written over the true state");
+    if (check_tick("srbm_controller_measure_dev", tick, tick_dt) || use_batch(h)) return -1;
+    return launch_measure(h, tick, tick_dt, q_dev, v_dev, qm_dev, vm_dev);
+}
+int srbm_sensor_philox_host(const int* counter4, const int* key2, int* out4) {
+    if (!counter4 || !key2 || !out4) return fail("srbm_sensor_philox_host: bad arguments");
+    uint32_t c[4], k[2], o[4];
+    std::memcpy(c, counter4, sizeof c); std::memcpy(k, key2, sizeof k);
+    srbm_philox4x32_10(c, k, o);
+    std::memcpy(out4, o, sizeof o);
+    return 0;
+}
+int srbm_sensor_state_init_host(int batch, const double* q, const double* v, double* ms) {
+    if (batch <= 0 || !q || !v || !ms) return fail("srbm_sensor_state_init_host: bad arguments");
+    for (size_t b = 0; b < (size_t)batch; b++) srbm_sensor_state_init(q + 19 * b, v + 18 * b, ms + SRBM_SENS_STATE_DOUBLES * b);
+    return 0;
+}
+int srbm_sensor_measure_host(int batch, int first_tick, int ticks, double tick_dt, const double* sens, const long long* seed, const double* q_true,
+                             const double* v_true, double* ms_inout, double* srec_inout, double* qm_out, double* vm_out) {
+    const char* fn = "srbm_sensor_measure_host";
+    if (batch <= 0 || !sens || !seed || !q_true || !v_true || !ms_inout || !srec_inout || !qm_out || !vm_out) return fail(std::string(fn) + ": bad arguments");
+    if (first_tick < 0 || ticks < 0 || ticks > INT_MAX - first_tick) return fail(std::string(fn) + ": first_tick >= 0 and ticks >= 0 are required");
+    if (!std::isfinite(tick_dt) || tick_dt <= 0.0) return fail(std::string(fn) + ": a finite tick_dt > 0 is required");
+    if (check_sensors(fn, batch, sens)) return -1;
+    const size_t B = batch;
+    std::vector<double> S(SRBM_SENS_DEV_DOUBLES * B);
+    for (size_t b = 0; b < B; b++) srbm_sensor_device_record(sens + SRBM_SENS_DOUBLES * b, S.data() + SRBM_SENS_DEV_DOUBLES * b);
+    for (int k = 0; k < ticks; k++)
+        for (size_t b = 0; b < B; b++) {
+            const size_t at = (size_t)k * B + b;
+            srbm_sensor_measure_one(S.data() + SRBM_SENS_DEV_DOUBLES * b, (unsigned long long)seed[b], first_tick + k, tick_dt, q_true + 19 * at, v_true + 18 * at,
+                                    ms_inout + SRBM_SENS_STATE_DOUBLES * b, srec_inout + SRBM_SENS_RECORD_DOUBLES * b, qm_out + 19 * at, vm_out + 18 * at);
+        }
+    return 0;
+}
 // MPCController::MPCUpdate's branch on the run number (mpc_controller.cpp:324-346) as srbm_gait_rti_advance has it, on the state, time and ee of
 // the tick (device arrays of the batch), with the record of the run where a step log is enabled
 static int gait_update(srbm_gait* g, int run, int F, const double* state, const double* time, const double* ee) {
@@ -2740,6 +2920,7 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
     if (!h->d_wb) return fail(fn + ": the whole-body plant state has not been set (srbm_wb_plant_set_state)");
     if (tick_usable(h)) return -1;
     if (h->fd_kind == 1 && !h->d_fd_act) return fail(fn + ": " + FD_NO_ACTUATORS);
+    if (h->d_sens && !h->sens_ready) return fail(fn + ": " + SENS_NO_STATE);
     if (h->contact_fb && !(h->fd_kind == 1 && h->d_ground))
         return fail(fn + ": contact feedback is on (srbm_controller_set_contact_feedback) and needs the torque-driven plant with a ground "
                     "(srbm_wb_plant_set_kind 1, srbm_wb_plant_set_ground): without a ground nothing measures a contact");
@@ -2770,6 +2951,7 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
     const size_t B = h->batch;
     const WbBuf w = wb_buf(h);
     hipLaunchKernelGGL(srbm_k_wb_tick_time, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, w.time + (first_tick & 1) * B, h->batch, first_tick, tick_dt);
+    const SensBuf sb = h->d_sens ? sens_buf(h) : SensBuf{};
     std::vector<char> pub_need;          // with a latency set: the ticks of update pub_need_u before which the publish kernel is launched
     long long pub_need_u = 0;
     for (int k = first_tick; k < first_tick + ticks; k++) {
@@ -2785,7 +2967,10 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
             if ((k == first_tick || pub_need[k - e * ticks_per_update - 1]) &&
                 launch_publish(h, time, (int)e, (double)(e * ticks_per_update) * tick_dt, update ? 1 : 0)) return -1;
         }
-        if (srbm_control_tick_dev(h, w.q, w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state, w.ee)) return -1;
+        // with sensors set the tick reads the measurement of (q, v), made now; the plant, the push, the ground and the tick-log head keep the truth
+        if (h->d_sens && launch_measure(h, k, tick_dt, w.q, w.v, sb.qm, sb.vm)) return -1;
+        if (srbm_control_tick_dev(h, h->d_sens ? sb.qm : w.q, h->d_sens ? sb.vm : w.v, time, w.control, w.sol, w.status, nullptr, nullptr, w.contact, w.state,
+                                  w.ee)) return -1;
         // mpc_controller.cpp:322: the contacts measured at t_k -- the ground's state after tick k - 1 -- re-time the plan the update starts from
         if (update && h->contact_fb && launch_contact_feedback(h, time, h->d_cs)) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};

@@ -267,6 +267,16 @@ int srbm_controller_get_latency_record(srbm_batch*, double*)
 int srbm_controller_get_published(srbm_batch*, int, int, srbm_trajectory*)
 int srbm_controller_publish_dev(srbm_batch*, dev*, int, double, int)
 int srbm_latency_publish_ticks_host(int, int, int, int, double, double*, int*, int, int*, int*)
+int srbm_controller_set_sensors(srbm_batch*, double*, long long*)
+int srbm_controller_get_sensors(srbm_batch*, double*, long long*)
+int srbm_controller_get_sensor_state(srbm_batch*, double*)
+int srbm_controller_set_sensor_state(srbm_batch*, double*)
+int srbm_controller_get_sensor_record(srbm_batch*, double*)
+int srbm_controller_get_measured(srbm_batch*, double*, double*)
+int srbm_controller_measure_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*)
+int srbm_sensor_philox_host(int*, int*, int*)
+int srbm_sensor_state_init_host(int, double*, double*, double*)
+int srbm_sensor_measure_host(int, int, int, double, double*, long long*, double*, double*, double*, double*, double*, double*)
 int srbm_get_sizes(srbm_batch*, int*)
 int srbm_get_status(srbm_batch*, int*, int*)
 int srbm_get_status_accumulated(srbm_batch*, int*)

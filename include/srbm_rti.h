@@ -562,8 +562,8 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *     3, 4      QP status, QP iterations
  *     5         flags: bit 0 the push was applied in this tick, bit 1 an MPC update followed this tick, bit 2 the plant coasted (plant kind 0
  *               only: the torque-driven plant never coasts on a zero control action), bit 3 a factorisation of the torque-driven plant broke down
- *     6..12     base position and quaternion of the measured q
- *     13..18    base twist of the measured v
+ *     6..12     base position and quaternion of the plant's q
+ *     13..18    base twist of the plant's v
  *     19..30    torques (control[24..36))
  *     31..42    contact forces per foot [4][3], unstacked from qp_sol, zero for a foot not in contact
  *     43..46    desired contacts [4]
@@ -586,6 +586,9 @@ int srbm_controller_advance(srbm_batch* h, int first_tick, int ticks, int ticks_
  *       63      4096 + word.  Bit i: foot i in ground contact; bit 4 + i: foot i slipping; bit 8 + i: the plan's contact flag of foot i
  *               (field 43 + i) differs from the ground's
  *     Fields 31..42 and 51..56 are the QP's forces and acceleration for either kind.
+ *     With sensors set (srbm_controller_set_sensors, below) the log keeps holding the truth: fields 6..18 are the plant's (q, v), not the measurement
+ *     the tick read, which is what lets srbm_tick_summary_fold judge a fall and not an estimate of one.  Fields 47..50 come from the tick's ee and are
+ *     therefore the feet of the measured q; every other field of 0..56 is an output of the tick that read the measurement.
  * The entries have the semantics of their srbm_step_log_* counterparts: srbm_tick_log_enable allocates max_ticks x batch records and sets the cursor to
  * 0 (0 disables and frees); capacity is checked before anything is launched; get (host, synchronous) and copy_dev (on the stream) fail for a slot
  * range outside [0, ticks_logged) and when no log is enabled.  A clone has logging off. */
@@ -958,6 +961,93 @@ int srbm_controller_get_published(srbm_batch* h, int first, int count, srbm_traj
 int srbm_controller_publish_dev(srbm_batch* h, const double* time_dev, int update_number, double t_start, int force);
 int srbm_latency_publish_ticks_host(int batch, int first_tick, int ticks, int ticks_per_update, double tick_dt, const double* lat, const int* iters, int n_updates,
                                     int* publish_tick, int* overrun);
+
+/* ---- sensor model: the control ticks of a rollout read a measurement of the plant's state, not the state ----
+ * The reference's robot (hardware/hardware_robot.cpp) takes the base pose from motion capture at its own, slower rate (:484-485, :506), the base
+ * linear velocity from a finite difference of the two newest samples (:507), the angular velocity from the gyro (:519-521), passes base and joint
+ * velocities through a first-order low-pass filter (:152-174, LPF at :676-679), and everything carries noise.  A setting of the batch, off by default;
+ * with it off every entry is byte for byte what it is without this section.  With it set, every control tick of srbm_controller_advance and
+ * srbm_gait_controller_advance reads a MEASURED (qm, vm) that one kernel (srbm_k_measure, csrc/srbm_sensors.hiph) makes from the plant's true (q, v)
+ * just before the tick -- and so do ReconstructState, the targets, the whole-body QP and the state / ee handed to the MPC update or the gait step.
+ * The plant, the push, the ground's contact state and contact feedback (the ground's cs: foot-force sensing is out of scope), the latency rule and
+ * the tick-log head (fields 0..46 and 51..56) keep working on the true state.
+ *
+ * sens[batch][16] and seed[batch] (64 bits, any value) per instance:
+ *     0        mocap_ticks, integer 1..64: the base pose is sampled on ticks k with k % mocap_ticks == 0 and held in between
+ *     1        mocap_delay, integer 0..3: the tick reads the sample taken that many samples before the newest
+ *     2, 3     sigma_p (m, per axis), sigma_r (rad, per axis) of a pose sample
+ *     4        base linear velocity source.  0: the plant's v[0..3).  1: the finite difference of the two newest available samples
+ *     5        sigma_v (m/s) of the linear velocity (source 0; source 1 inherits the pose noise)
+ *     6, 7..9  gyro sigma_w, gyro bias[3]
+ *     10, 11   sigma_qj, sigma_vj of the twelve joint angles / rates
+ *     12, 13   low-pass x of the six base velocities and of the joint rates, 0: no filter; x = tan(pi fpass / fsample) in the reference
+ *     14, 15   0
+ * Refused, naming instance and field, the batch untouched: a value that is not finite; a negative sigma or x; a count that is no integer or out of
+ * range; a source other than 0 / 1; entries 14, 15 not 0.
+ *
+ * Noise.  Counter-based, so a rollout cut anywhere is the same rollout: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9, 0xBB67AE85), key (low, high word of the instance's seed), counter (tick k, channel c, 0, 0).  The four output words are summed exactly
+ * in 64 bits, s converts to double exactly, and z = (s 2^-32 - 2) * 1.7320508075688772: zero mean, unit variance, |z| <= 2 sqrt(3), the same bits
+ * on host and device.  Channels: 0..2 position, 3..5 orientation, 6..8 linear velocity, 9..11 gyro, 12..23 joint angles, 24..35 joint rates.
+ * A channel whose sigma is 0 copies its input -- no arithmetic on it at all -- and so does a gyro axis whose bias is 0.
+ * Every rounded operation below is one IEEE operation, in the order written.
+ * Pose.  On a sample tick: position p + sigma_p z; orientation q (x) (delta / 2, 1), delta = sigma_r z, the terms of each component in the order of
+ *     x = a3 b0 + a0 b3 + a1 b2 - a2 b1,  y = a3 b1 - a0 b2 + a1 b3 + a2 b0,  z = a3 b2 + a0 b1 - a1 b0 + a2 b3,  w = a3 b3 - a0 b0 - a1 b1 - a2 b2
+ * (xyzw, a = q, b3 = 1) summed left to right, then scaled by (3 - |.|^2) / 2, the squares summed x, y, z, w; skipped altogether at sigma_r == 0.
+ * The sample goes into slot n % 5 of a ring of 5, n the samples taken before.  The tick's base pose is the ring entry mocap_delay behind the newest.
+ * The ring is pre-filled with the true initial pose, so early ticks read that.
+ * Linear velocity, source 1: (p_avail - p_prev) / (mocap_ticks * tick_dt), the ring entries at and one behind the available one, each component
+ * divided, then rotated into the frame of the plant's v[0..3) -- the body frame -- by the transpose of the available sample's rotation matrix
+ * (R = Eigen's Quaterniond::matrix(); component i is R0i w0 + R1i w1 + R2i w2 left to right, Rii = 1 - 2 (. + .), Rij = 2 (. +- .)).  It is zero
+ * while the two entries are the pre-fill.
+ * Gyro: omega + bias + sigma_w z.  Joints: q_j + sigma_qj z, v_j + sigma_vj z.
+ * Filter, once per tick and velocity component: out = (x (cur + prev) + (1 - x) prev_out) / (x + 1), formed as a (cur + prev) + c prev_out with
+ * a = x / (1 + x), c = (1 - x) / (1 + x) computed once on the host; prev and prev_out start at the true initial v; x == 0: out = cur.
+ * The transparent model -- count 1, delay 0, source 0, no sigma, no bias, no filter -- makes (qm, vm) the bytes of (q, v).
+ *
+ * Sensor state ms[batch][72], carried from tick to tick in the batch:
+ *     0            pose samples taken
+ *     1 + 7 s + i  component i of ring slot s = 0..4: position [3], quaternion xyzw [4]
+ *     36 + j       the filter's prev of velocity component j = 0..17 (the unfiltered measurement of the last tick)
+ *     54 + j       the filter's prev_out (the measurement of the last tick)
+ * Sensor record srec[batch][8] since the state was set:
+ *     0, 1         ticks measured, pose samples taken
+ *     2..7         running maxima of |pm - p|_inf, 1 - (qm . q)^2 (0 where qm equals q component for component), |vm_lin - v_lin|_inf,
+ *                  |wm - w|_inf, |qm_j - q_j|_inf, |vm_j - v_j|_inf
+ *
+ * srbm_controller_set_sensors: NULL sens removes the setting and frees its buffers; otherwise stores the setting and starts the sensor state, the
+ * record (zero) and the last measurement from the plant's state as it is after the work queued so far (without a plant state: at
+ * srbm_wb_plant_set_state).  srbm_wb_plant_set_state re-initialises state and record from the state being set; srbm_batch_clone carries setting,
+ * state, record and last measurement.  srbm_controller_get_sensors: the setting back.  _get_sensor_state / _set_sensor_state: ms[batch][72]
+ * (set: the sample count must be an integer 0 .. 2^52).  _get_sensor_record: srec[batch][8].  _get_measured: the last (qm[batch][19], vm[batch][18]);
+ * either may be NULL.  All refused without the setting.
+ * srbm_controller_measure_dev: the kernel alone on the caller's true q_dev[batch][19], v_dev[batch][18] and output arrays (which must not be the
+ * inputs), for tests and host-driven chains: it advances the batch's sensor state and record by tick `tick`.  One launch on the batch's stream, no
+ * copy, no synchronisation.  Refused without the setting, before a plant state was set, for tick < 0 or a tick_dt that is not finite and > 0.
+ * In srbm_controller_advance the kernel runs directly before srbm_control_tick_dev of tick k (after a latency publication, if any) and the tick
+ * gets the batch's (qm, vm) in the place of the plant's arrays; nothing else in the loop changes.
+ * What it is NOT: no foot-force or contact sensing (contact feedback keeps reading the ground); no accelerometer; no state estimator beyond the
+ * reference's differencing and filtering; no dropped packets; the reference's substitution for a packet that was not updated (:142-144) is not
+ * modelled.
+ *
+ * Three entries need no GPU.  srbm_sensor_philox_host: one Philox4x32-10 block, words as bit patterns.  srbm_sensor_state_init_host:
+ * ms[batch][72] of plants at q[batch][19], v[batch][18].  srbm_sensor_measure_host: the same model function the kernel compiles, over a recorded
+ * sequence q_true[ticks][batch][19], v_true[ticks][batch][18] for ticks first_tick .. first_tick + ticks - 1: ms_inout and srec_inout move,
+ * qm_out[ticks][batch][19] and vm_out[ticks][batch][18] are written.  Refused as srbm_controller_set_sensors refuses. */
+#define SRBM_SENSOR_DOUBLES 16
+#define SRBM_SENSOR_STATE_DOUBLES 72
+#define SRBM_SENSOR_RECORD_DOUBLES 8
+int srbm_controller_set_sensors(srbm_batch* h, const double* sens, const long long* seed);
+int srbm_controller_get_sensors(srbm_batch* h, double* sens, long long* seed);
+int srbm_controller_get_sensor_state(srbm_batch* h, double* ms);
+int srbm_controller_set_sensor_state(srbm_batch* h, const double* ms);
+int srbm_controller_get_sensor_record(srbm_batch* h, double* srec);
+int srbm_controller_get_measured(srbm_batch* h, double* q, double* v);
+int srbm_controller_measure_dev(srbm_batch* h, int tick, double tick_dt, const double* q_dev, const double* v_dev, double* qm_dev, double* vm_dev);
+int srbm_sensor_philox_host(const int* counter4, const int* key2, int* out4);
+int srbm_sensor_state_init_host(int batch, const double* q, const double* v, double* ms);
+int srbm_sensor_measure_host(int batch, int first_tick, int ticks, double tick_dt, const double* sens, const long long* seed, const double* q_true,
+                             const double* v_true, double* ms_inout, double* srec_inout, double* qm_out, double* vm_out);
 
 /* ---- results (all copied to host) ---- */
 /* sizes[batch][8] = n, m, n_eq, n_ineq, n_force_vars, n_pos_vars, n_td_rows, n_force_samples */

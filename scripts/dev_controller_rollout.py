@@ -26,6 +26,10 @@ medians and spreads.
                  (srbm_controller_publish_dev), 200 launches in which every instance is published (a new update number each, forced) and 200 in
                  which none is (the same update number again); and (b) with latency 0 set and the publish kernel launched before every tick: the same
                  rollout as (b), so the difference is what a launch per tick costs.  Skipped, with a note, on a library without the setting
+  (s) sensors    (a) logged with sensors set (srbm_controller_set_sensors): the transparent model, whose rollout is (a)'s, so the difference is what the
+                 measure kernel's launch per tick costs; everything on (mocap every 5 ticks one sample late, pose noise, finite-difference velocity,
+                 gyro noise and bias, joint noise, both filters), another rollout, with the iterations of its whole-body QP; and the measure kernel
+                 alone (srbm_controller_measure_dev), 200 launches with everything on.  Skipped, with a note, on a library without the setting
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -69,6 +73,13 @@ def main():
         res.update({'latency_0': [], 'latency_20ms': [], 'latency_per_iteration': [], 'chain_latency_0_every_tick': [], 'publish_all': [], 'publish_none': []})
     if has_terrain:
         res.update({'terrain_s4_logged': [], 'terrain_step_s1': [], 'terrain_step_s4': []})
+    has_sensors = hasattr(ControllerRollout, 'set_sensors')
+    if has_sensors:
+        from srbm_loader import sensors
+        res.update({'sensors_transparent': [], 'sensors_all': [], 'measure': []})
+        sens_transparent = sensors.record()
+        sens_all = sensors.record(mocap_ticks=5, mocap_delay=1, sigma_p=1e-3, sigma_r=2e-3, velocity_source=1, sigma_w=0.01, gyro_bias=(0.01, -0.01, 0.005),
+                                  sigma_qj=1e-3, sigma_vj=0.05, lpf_base=sensors.lpf_x(40.0, DT), lpf_joints=sensors.lpf_x(100.0, DT))
     ground = terrain = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
@@ -217,6 +228,20 @@ def main():
                               updates=int(steps.shape[0]), mean_ipm_iterations=float(steps[:, :, 11].mean()),
                               slowest_ipm_iterations_mean=float(steps[:, :, 11].max(axis=1).mean()), publications=int(rec[:, 1].sum()), overruns=int(rec[:, 2].sum()),
                               max_latency=float(rec[:, 6].max()), mean_age_at_publication=float((rec[:, 7] / np.maximum(rec[:, 1], 1)).mean()))
+        # (s) the logged entry with sensors set: the transparent model, and everything on
+        for name, sens in (('sensors_transparent', sens_transparent), ('sensors_all', sens_all)) if has_sensors else ():
+            g, R = fresh(TICKS + 3)
+            R.set_sensors(sens, np.arange(B))
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log, srec = R.tick_log(), R.sensor_record()
+            info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), mean_qp_iterations=float(log[:, :, F['qp_iters']].mean()),
+                              slowest_qp_iterations_mean=float(log[:, :, F['qp_iters']].max(axis=1).mean()),
+                              coasted_ticks=int(((log[:, :, F['flags']].astype(int) & FLAG_COAST) != 0).sum()),
+                              base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())], samples=int(srec[:, 1].sum()),
+                              max_errors=[float(x) for x in srec[:, 2:].max(axis=0)])
         # (b) the same loop from the host, on torch's buffers, on the batch's stream
         g, R = fresh()
         T = ControlTick(g)
@@ -302,6 +327,21 @@ def main():
                     res[name].append(timed(g, fn))
                 info['publish_all_publications'] = int(R.latency_record()[:, 1].sum())
                 R.set_latency(None)
+            # ... and the measure kernel alone, everything on, on the same true state every launch
+            if has_sensors:
+                R.set_sensors(sens_all, np.arange(B))
+                q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64))
+                qm_d, vm_d = torch.zeros((B, 19), **f64), torch.zeros((B, 18), **f64)
+
+                def measure():
+                    for k in range(TICKS):
+                        R.measure_dev(k, DT, q_d.data_ptr(), v_d.data_ptr(), qm_d.data_ptr(), vm_d.data_ptr())
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                measure()
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                res['measure'].append(timed(g, measure))
+                info['measure_ticks'] = int(R.sensor_record()[:, 0].sum())
+                R.set_sensors(None)
         # ... and what a launch before EVERY tick costs in a rollout that is otherwise (b): the chain with latency 0 set, the publish kernel launched before
         # every tick (it publishes before the tick after an update and returns on its decision before every other one)
         if has_latency:
@@ -333,6 +373,8 @@ def main():
         info['terrain'] = 'this library has no terrain: rows (t) skipped'
     if not has_latency:
         info['latency'] = 'this library has no latency setting: rows (l) skipped'
+    if not has_sensors:
+        info['sensors'] = 'this library has no sensor model: rows (s) skipped'
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
                           spread_ms={k: float(max(v) - min(v)) for k, v in res.items()}, **info)))
 
