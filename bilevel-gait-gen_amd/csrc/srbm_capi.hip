@@ -1149,6 +1149,14 @@ int srbm_update_contact_times(srbm_batch* h, const double* times, int max_contac
     return srbm_synchronize(h);
 }
 
+// A solve that kernel 1 refused for capacity (SRBM_ERR_CAPACITY, status Other) assembled no QP: the sizes in the instance record and the counts in
+// the work record are those of the schedule that did NOT fit, and nothing may be expanded or indexed by them (the debug exports refuse).
+static bool refused_for_capacity(const SrbmInst& I) { return (I.err & SRBM_ERR_CAPACITY) != 0 && I.status == SRBM_OTHER; }
+static std::string refused_message(const char* fn, int inst) {
+    return std::string(fn) + ": the last solve of instance " + std::to_string(inst) + " was refused for capacity (SRBM_ERR_CAPACITY, status 8): "
+           "no QP was assembled, its sizes belong to a schedule the build does not hold";
+}
+
 // ---------------- bilevel (gait) step: mpc::GaitOptimizer for the batch ----------------
 struct srbm_gait {
     srbm_batch* h = nullptr;        // the instances being optimised
@@ -1159,6 +1167,7 @@ struct srbm_gait {
     int* ready = nullptr;                                                         // [B] deriv_ready of the controller
     SrbmGaitWork* gw = nullptr;                                                   // sensitivity workspace, one per instance
     unsigned ls_gen = 0;                                                          // params_gen of h the candidates' records were derived from
+    bool times_read = false;        // xk / counts hold contact times read from a trajectory (srbm_gait_set_contact_times_from_trajectory ran since creation)
 };
 
 // the parameters of the candidate batch: candidate w = b * LS_SIZE + c solves with instance b's record
@@ -1240,6 +1249,7 @@ int srbm_gait_set_contact_times_from_trajectory(srbm_gait* g) {
     if (use_batch(h)) return -1;
     hipLaunchKernelGGL(srbm_k_gait_read_contact_times, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, g->xk, g->counts);
     HIPCHK(hipGetLastError());
+    g->times_read = true;
     return 0;
 }
 int srbm_gait_get_contact_times(srbm_gait* g, double* xk, int* counts) {
@@ -1291,6 +1301,7 @@ int srbm_gait_get_param_partials(srbm_batch* h, int inst, int ee, int idx, doubl
     if (use_batch(h)) return -1;
     SrbmInst I;
     if (fetch(h, {{&I, h->insts + inst, sizeof(SrbmInst)}})) return -1;
+    if (refused_for_capacity(I)) return fail(refused_message("srbm_gait_get_param_partials", inst));
     const size_t n = I.n, me = I.n_eq, mi = I.n_ineq;
     if (n == 0 || me == 0) return fail("srbm_gait_get_param_partials: no QP has been solved yet");
     double* d = nullptr;
@@ -1345,7 +1356,7 @@ static void launch_gait_lp(srbm_gait* g) {
 // deriv_ready of every instance: `force` (0 / 1), or -1 for "a gradient exists and its LP was solved"
 static void launch_gait_ready(srbm_gait* g, int force) {
     srbm_batch* h = g->h;
-    hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, g->valid, g->lp_status, g->ready, force);
+    hipLaunchKernelGGL(srbm_k_gait_ready, dim3((h->batch + 63) / 64), dim3(64), 0, h->stream, h->dp, h->insts, g->valid, g->lp_status, g->ready, force);
 }
 // GaitOptimizer::OptimizeContactTimes (gait_optimizer.cpp:185-364): the LP over the contact-time step; time[batch]
 int srbm_gait_optimize_contact_times(srbm_gait* g, const double* time) {
@@ -1374,7 +1385,7 @@ static int line_search_core(srbm_gait* g, bool use_ready_mask) {
                        g->xk, g->step, h->d_state, h->d_time, h->d_ee, ls->d_state, ls->d_time, ls->d_ee, ready);
     HIPCHK(hipGetLastError());
     if (launch_step(ls)) return -1;
-    hipLaunchKernelGGL(srbm_k_gait_select, dim3(B), dim3(128), 0, h->stream, h->dp, h->insts, ls->insts, ready, g->imin, g->costs);
+    hipLaunchKernelGGL(srbm_k_gait_select, dim3(B), dim3(128), 0, h->stream, h->dp, h->insts, ls->insts, h->works, ls->works, ready, g->imin, g->costs);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1382,6 +1393,10 @@ static int line_search_core(srbm_gait* g, bool use_ready_mask) {
 int srbm_gait_line_search(srbm_gait* g, const double* state, const double* time, const double* ee, int* imin, double* costs) {
     if (!g || !state || !time || !ee) return fail("bad arguments");
     srbm_batch* h = g->h;
+    // every candidate's schedule is x_k + (i/10) step: with x_k never read, the zeros of the allocation (no ready mask here to keep the schedules)
+    if (!g->times_read)
+        return fail("srbm_gait_line_search: this handle has not read any contact times since it was created -- call "
+                    "srbm_gait_set_contact_times_from_trajectory (or srbm_gait_compute_gradient, which does) first");
     HIPCHK(hipSetDevice(h->device));
     if (upload_inputs(h, state, time, ee)) return -1;
     if (line_search_core(g, false)) return -1;
@@ -1765,6 +1780,7 @@ int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* Pm, do
     if (fetch(h, {{vi.data(), h->insts + inst, sizeof(SrbmInst)}, {vw.data(), h->works + inst, sizeof(SrbmWork)}})) return -1;
     const SrbmInst& I = vi[0];
     const SrbmWork& W = vw[0];
+    if (refused_for_capacity(I)) return fail(refused_message("srbm_export_qp", inst));
     const SrbmParams P = inst_params(h, inst);
     const int N = P.N, n = I.n, m = I.m, nx = (N + 1) * 12, ns = W.n_samp;
     const double dt = P.dt;

@@ -409,11 +409,16 @@ int srbm_gait_get_step(srbm_gait* g, double* step);
 /* GaitOptimizer::LineSearch (gait_optimizer.cpp:671-753): 10 schedules x_k + (i/10) step per instance, each a full
  * MPC::GetRealTimeUpdate(state, time, ee) on a copy of the instance (inputs as srbm_get_real_time_update); the cheapest
  * candidate (cost / n, primal-infeasible ones excluded, index 0 if all are) is installed with
- * MPC::SetWarmStartTrajectory.  imin[batch], costs[batch][10] may be NULL. */
+ * MPC::SetWarmStartTrajectory.  imin[batch], costs[batch][10] may be NULL.
+ * Refused, with nothing launched, on a handle that has not read contact times since srbm_gait_create (x_k would be the zeros of the
+ * allocation): srbm_gait_set_contact_times_from_trajectory reads them, and so do srbm_gait_compute_gradient and the gradient runs of
+ * srbm_gait_rti_advance, srbm_gait_closed_loop_advance and srbm_gait_controller_advance.  (The line-search runs of those three entries need no
+ * contact times in the handle for an instance that is not ready: its candidates keep the instance's schedule bit for bit.) */
 int srbm_gait_line_search(srbm_gait* g, const double* state, const double* init_time, const double* ee, int* imin, double* costs);
 /* The MPC loop of the controller with the gait step folded in (controllers/mpc_controller.cpp:320-346), device
  * resident and open loop like srbm_rti_advance (test/gait_opt_playground.cpp:113-126): for run_num = first_run_num ...
- *   run_num % gait_opt_freq == 0, run_num > 0 : GaitOptimizer::LineSearch where a gradient is ready (plain update elsewhere)
+ *   run_num % gait_opt_freq == 0, run_num > 0 : GaitOptimizer::LineSearch where a gradient is ready (elsewhere the plain update, bit for bit: the
+ *                                               instance's schedule is not rewritten, its whole record and work record become candidate 0's)
  *   (run_num + 1) % gait_opt_freq == 0        : MPC::GetRealTimeUpdate, then MPCController::GaitOpt (gradient + LP)
  *   otherwise                                 : MPC::GetRealTimeUpdate
  * Asynchronous on the batch's stream; srbm_synchronize(h) to wait. */
@@ -1057,7 +1062,23 @@ int srbm_get_sizes(srbm_batch* h, int* sizes);
  * 2 time beyond the last knot, 4 invalid time, 8 force node not mutable, 16 beyond the capacity of the build (status Other), 32 RemovePoly on an empty
  * spline, 64 touch-down index, 128 a pivot of the normal matrix was regularised, 256 internal invariant violated (a dense state row with a non-zero
  * outside the force variables of its coordinate: never observed; the compact storage of those rows rests on it), 512 a bounded wait of the step
- * queue ran out (multi-step launches of a batch larger than the chip hand out (instance, step) items to a resident grid; never observed). */
+ * queue ran out (multi-step launches of a batch larger than the chip hand out (instance, step) items to a resident grid; never observed).
+ *
+ * Refused solves and the gait step.  A schedule that needs more spline variables, force samples or knots per foot than the build holds
+ * (srbm_get_capacity) is REFUSED by the assembly: status 8 (Other), bit 16, one solve counted as not solved.  No QP was assembled: the instance's
+ * trajectory (node states, knot tables, init_time) and its last solution stay those of its last accepted solve, while srbm_get_sizes reports the
+ * sizes of the schedule that did not fit.  Until the instance's next solve:
+ *   - condensing, the interior-point solve and the update return at once, in the one-step and in the multi-step launches (every later step
+ *     of a multi-step launch assembles again -- and is refused again while the schedule stays);
+ *   - srbm_gait_compute_sensitivity leaves the instance's sensitivity workspace as it was (only its LU-failure flag is set) and
+ *     srbm_gait_get_sensitivity returns a zero row for it; srbm_gait_compute_gradient writes a zero gradient row and valid = 0; the instance is
+ *     never "ready" in the advance entries, whatever srbm_gait_set_gradient supplied: a line-search run gives it the plain update (refused again,
+ *     imin = -1).  Bit 16 raised by the gait step itself (more than 32 contact times per instance, more than 16 per foot) has the same effect;
+ *   - srbm_gait_line_search has no ready mask: the instance's ten candidates solve x_k + (i/10) step like any other's -- those that do not fit
+ *     are refused one by one (srbm_gait_get_candidate_status), one that fits may win;
+ *   - srbm_export_qp and srbm_gait_get_param_partials fail ("... was refused for capacity ...") and write nothing;
+ *   - every other read-back entry, the step-log and tick kernels and srbm_pack_results bound their loops by the capacities of the build, not by
+ *     the sizes of the instance, and show the last accepted solve. */
 int srbm_get_status(srbm_batch* h, int* status, int* err);
 /* Sticky accumulators over every solve since creation / the last clear (multi-step launches overwrite status and err each
  * step; the step log, srbm_step_log_*, keeps both per step): acc[batch][4] = {all error bits raised, solves, solves not in {Solved, SolvedInacc},
