@@ -25,6 +25,9 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
                                           R.set_latency(base[batch], per_iteration) -- base + per_iteration * (IPM iterations of the solve)
     R.set_sensors(sens, seed)             optional: the ticks read a measurement of (q, v) -- mocap rate and delay, noise, gyro bias, low-pass filters --
                                           sens[batch][16] from srbm_loader.sensors.record(...), one 64-bit seed per instance
+    R.set_joints(joints, stops)           optional, with set_plant(1, ...): a joint model -- damping, armature, dry friction, range stops, motor lag --
+                                          joints[batch][12][8] from srbm_loader.joints.record(...) or joints.a1_model(), stops = (k_l, d_l)
+    js = R.joint_state(); jrec = R.joint_record()
     q, v = R.state(); log = R.tick_log(); pub = R.latency_record(); qm, vm = R.measured(); srec = R.sensor_record()"""
 import ctypes as C
 
@@ -53,6 +56,8 @@ LATENCY_RECORD_FIELDS = dict(update_in_force=0, publications=1, overruns=2, last
 PLANT_QP_ACCELERATION, PLANT_TORQUE_DRIVEN = 0, 1
 _llp = C.POINTER(C.c_longlong)
 SENSOR_DOUBLES, SENSOR_STATE_DOUBLES, SENSOR_RECORD_DOUBLES = 16, 72, 8          # set_sensors: the setting, the state and the record of an instance
+JOINT_DOUBLES, JOINT_STOP_DOUBLES, JOINT_RECORD_DOUBLES = 8, 2, 8                # set_joints: a joint, an instance's stops, its record
+JOINT_RECORD_FIELDS = dict(substeps=0, substeps_beyond_range=1, max_excursion=2, max_friction_torque=3, max_motor_lag=4, joints_beyond_range=5)
 SENSOR_RECORD_FIELDS = dict(ticks=0, samples=1, max_position=2, max_orientation=3, max_linear_velocity=4, max_angular_velocity=5, max_joint_angle=6,
                             max_joint_rate=7)
 
@@ -273,6 +278,44 @@ class ControllerRollout:
         """the torque-driven plant step alone on device pointers (ints): q[batch][19], v[batch][18] in place from control[batch][36],
         contact[batch][4], status[batch][2] of control_tick_dev; sol: None or [batch][30] <- (a, F) of the last sub-step; asynchronous, never logs"""
         self.mpc._chk(self.L.srbm_wb_fd_step_dev(self.mpc.h, int(tick), float(tick_dt), q, v, control, contact, status, sol))
+
+    # ---- the joint model of the torque-driven plant ----
+    def set_joints(self, joints, stops=None):
+        """a joint model for the torque-driven plant (srbm_wb_plant_set_joints): joints one [12][8] or [batch][12][8], per joint b, I_a, f_c, v_s,
+        q_min, q_max, T, 0 (joints.record builds one from physical values), stops one [2] or [batch][2] = k_l, d_l.  joints None removes the setting"""
+        m = self.mpc
+        if joints is None:
+            m._chk(self.L.srbm_wb_plant_set_joints(m.h, None, None))
+            return
+        if stops is None:
+            raise ValueError('a joint model needs the compliance of its stops: stops = (k_l, d_l)')
+        m._chk(self.L.srbm_wb_plant_set_joints(m.h, _d(m._bcast(joints, 12 * JOINT_DOUBLES)), _d(m._bcast(stops, JOINT_STOP_DOUBLES))))
+
+    def joints(self):
+        """-> joints[batch][12][8], stops[batch][2] as set"""
+        m = self.mpc
+        j, s = np.zeros((m.batch, 12, JOINT_DOUBLES)), np.zeros((m.batch, JOINT_STOP_DOUBLES))
+        m._chk(self.L.srbm_wb_plant_get_joints(m.h, _d(j), _d(s)))
+        return j, s
+
+    def joint_state(self):
+        """-> js[batch][12]: the motor torques after the work queued so far"""
+        m = self.mpc
+        js = np.zeros((m.batch, 12))
+        m._chk(self.L.srbm_wb_plant_get_joint_state(m.h, _d(js)))
+        return js
+
+    def set_joint_state(self, js):
+        """one [12] or [batch][12] (set_joints and set_state reset it to zero)"""
+        m = self.mpc
+        m._chk(self.L.srbm_wb_plant_set_joint_state(m.h, _d(m._bcast(js, 12))))
+
+    def joint_record(self):
+        """-> jrec[batch][8] (JOINT_RECORD_FIELDS) after the work queued so far"""
+        m = self.mpc
+        jrec = np.zeros((m.batch, JOINT_RECORD_DOUBLES))
+        m._chk(self.L.srbm_wb_plant_get_joint_record(m.h, _d(jrec)))
+        return jrec
 
     # ---- the ground of the torque-driven plant ----
     def set_ground(self, ground):

@@ -25,6 +25,7 @@
 #include "srbm_wb_fd.hiph"
 #include "srbm_wb_ground.hiph"
 #include "srbm_wb_terrain.hiph"
+#include "srbm_wb_joints.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_mpc_latency.hiph"
 #include "srbm_sensors.hiph"
@@ -141,6 +142,9 @@ struct srbm_batch {
     bool sens_ready = false;         // the sensor state was initialised from a plant state
     std::vector<double> sens;        // host copy of the caller's sens[batch][SRBM_SENS_DOUBLES]
     std::vector<unsigned long long> sens_seed;
+    // the joint model of the torque-driven plant (srbm_wb_joints.hiph, srbm_wb_plant_set_joints): one allocation, nullptr: no joint model set
+    double* d_joints = nullptr;      // joints[batch][12][8], stops[batch][2], js[batch][12], jrec[batch][8]: joint_buf()
+    std::vector<double> joints;      // host copy of the caller's joints, then stops
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -480,7 +484,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
-    (void)hipFree(h->d_sens);
+    (void)hipFree(h->d_sens); (void)hipFree(h->d_joints);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -516,6 +520,15 @@ static SensBuf sens_buf(const srbm_batch* h) {
     s.S = h->d_sens; s.ms = s.S + SRBM_SENS_DEV_DOUBLES * B; s.srec = s.ms + SRBM_SENS_STATE_DOUBLES * B; s.qm = s.srec + SRBM_SENS_RECORD_DOUBLES * B;
     s.vm = s.qm + 19 * B; s.seed = reinterpret_cast<unsigned long long*>(s.vm + 18 * B);
     return s;
+}
+// the buffers of the joint model, one allocation: the setting (joints, stops), the motor torques and the record
+struct JointBuf { double *joints, *stops, *js, *jrec; };
+enum { JOINT_BUF_DOUBLES = WBJ_INSTANCE_DOUBLES + WBJ_STOP_DOUBLES + 12 + WBJ_RECORD_DOUBLES };
+static JointBuf joint_buf(const srbm_batch* h) {
+    const size_t B = h->batch;
+    JointBuf j;
+    j.joints = h->d_joints; j.stops = j.joints + WBJ_INSTANCE_DOUBLES * B; j.js = j.stops + WBJ_STOP_DOUBLES * B; j.jrec = j.js + 12 * B;
+    return j;
 }
 static int wb_alloc(srbm_batch* h) {
     const size_t B = h->batch;
@@ -689,6 +702,10 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     // (... and the sensor setting with the sensor state, its record and the last measurement)
     h->sens = src->sens; h->sens_seed = src->sens_seed; h->sens_ready = src->sens_ready;
     if (ok && src->d_sens) ok = hipMalloc(&h->d_sens, sens_bytes(B)) == hipSuccess && cp(h->d_sens, src->d_sens, sens_bytes(B));
+    // (... and the joint model with the motor torques and its record)
+    h->joints = src->joints;
+    if (ok && src->d_joints)
+        ok = hipMalloc(&h->d_joints, sizeof(double) * JOINT_BUF_DOUBLES * B) == hipSuccess && cp(h->d_joints, src->d_joints, sizeof(double) * JOINT_BUF_DOUBLES * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2300,6 +2317,7 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     HIPCHK(hipMemcpyAsync(w.q, q, sizeof(double) * 19 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(w.v, v, sizeof(double) * 18 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_cs, 0, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch, h->stream));          // no foot in contact
+    if (h->d_joints) HIPCHK(hipMemsetAsync(joint_buf(h).js, 0, sizeof(double) * (12 + WBJ_RECORD_DOUBLES) * (size_t)h->batch, h->stream));   // motors at rest, record empty
     std::vector<double> fb(SRBM_FB_DOUBLES * (size_t)h->batch);                                                   // no touch-down moved
     for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
@@ -2406,6 +2424,8 @@ static int fd_usable(srbm_batch* h, const char* fn) {
 // cs is nullptr; contact (on a ground: the plan's) and qp_sol are the tick's, for the record; lg: the record of the tick, nullptr: the unlogged kernel.
 // On a ground with a terrain in force (terrain_in_force) the step is the terrain's
 static bool terrain_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_ground && h->d_terrain; }
+// With a joint model in force (joints_in_force) every step and every solve of kind 1 is the joint model's instantiation (srbm_wb_joints.hiph)
+static bool joints_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_joints; }
 static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
                             const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
     const double* push = h->push_set ? h->d_push : nullptr;
@@ -2415,7 +2435,19 @@ static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, 
     const SrbmGroundArgs ga{h->d_ground, cs};
     const SrbmTickLogArgs l = lg ? *lg : SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0};
     const dim3 grid(h->batch), block(WBC_THREADS);
-    if (cs && terrain_in_force(h)) {
+    if (joints_in_force(h)) {
+        const JointBuf jb = joint_buf(h);
+        const SrbmJointArgs ja{jb.joints, jb.stops, jb.js, jb.jrec};
+        if (cs && terrain_in_force(h)) {
+            if (lg) hipLaunchKernelGGL((srbm_k_wb_terrain_joint_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, ja, tick, tick_dt, push, q, v, status, time_next, l);
+            else hipLaunchKernelGGL((srbm_k_wb_terrain_joint_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, ja, tick, tick_dt, push, q, v, status, time_next, l);
+        }
+        else if (cs && lg) hipLaunchKernelGGL((srbm_k_wb_ground_joint_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, ja, tick, tick_dt, push, q, v, status, time_next, l);
+        else if (cs) hipLaunchKernelGGL((srbm_k_wb_ground_joint_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, ja, tick, tick_dt, push, q, v, status, time_next, l);
+        else if (lg) hipLaunchKernelGGL((srbm_k_wb_fd_joint_step<true>), grid, block, 0, h->stream, h->dp, fa, ja, tick, tick_dt, push, q, v, status, time_next, l);
+        else hipLaunchKernelGGL((srbm_k_wb_fd_joint_step<false>), grid, block, 0, h->stream, h->dp, fa, ja, tick, tick_dt, push, q, v, status, time_next, l);
+    }
+    else if (cs && terrain_in_force(h)) {
         if (lg) hipLaunchKernelGGL((srbm_k_wb_terrain_step<true>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, tick, tick_dt, push, q, v, status, time_next, l);
         else hipLaunchKernelGGL((srbm_k_wb_terrain_step<false>), grid, block, 0, h->stream, h->dp, fa, ga, h->d_terrain, tick, tick_dt, push, q, v, status, time_next, l);
     }
@@ -2431,7 +2463,11 @@ int srbm_wb_forward_dynamics_dev(srbm_batch* h, const double* q_dev, const doubl
     if (fd_usable(h, "srbm_wb_forward_dynamics") || use_batch(h)) return -1;
     int stride = 0;
     const SrbmBody* bodies = fd_bodies(h, &stride);
-    hipLaunchKernelGGL(srbm_k_wb_forward_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, q_dev, v_dev, tau_dev, contact_dev, sol_dev, status_dev);
+    if (joints_in_force(h))
+        hipLaunchKernelGGL(srbm_k_wb_forward_dynamics_joint, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_joints, q_dev, v_dev, tau_dev,
+                           contact_dev, sol_dev, status_dev);
+    else
+        hipLaunchKernelGGL(srbm_k_wb_forward_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, q_dev, v_dev, tau_dev, contact_dev, sol_dev, status_dev);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2586,7 +2622,13 @@ int srbm_wb_ground_dynamics_dev(srbm_batch* h, const double* q_dev, const double
     if (ground_usable(h, "srbm_wb_ground_dynamics") || use_batch(h)) return -1;
     int stride = 0;
     const SrbmBody* bodies = fd_bodies(h, &stride);
-    if (terrain_in_force(h))
+    if (joints_in_force(h) && terrain_in_force(h))
+        hipLaunchKernelGGL((srbm_k_wb_ground_dynamics_joint<true>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_joints, h->d_ground,
+                           h->d_terrain, q_dev, v_dev, tau_dev, cs_in_dev, sol_dev, cs_out_dev, status_dev);
+    else if (joints_in_force(h))
+        hipLaunchKernelGGL((srbm_k_wb_ground_dynamics_joint<false>), dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_joints, h->d_ground,
+                           (const double*)nullptr, q_dev, v_dev, tau_dev, cs_in_dev, sol_dev, cs_out_dev, status_dev);
+    else if (terrain_in_force(h))
         hipLaunchKernelGGL(srbm_k_wb_terrain_dynamics, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, bodies, stride, h->d_ground, h->d_terrain, q_dev, v_dev,
                            tau_dev, cs_in_dev, sol_dev, cs_out_dev, status_dev);
     else
@@ -2625,6 +2667,130 @@ int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_d
     if (!h->d_fd_act) return fail(std::string("srbm_wb_ground_step_dev: ") + FD_NO_ACTUATORS);
     if (use_batch(h)) return -1;
     return launch_wb_torque(h, tick, tick_dt, q_dev, v_dev, cs_dev, control_dev, nullptr, status_dev, nullptr, sol_dev, nullptr, nullptr);
+}
+// ---- the joint model of the torque-driven plant (srbm_wb_joints.hiph) ----
+static_assert(SRBM_JOINT_DOUBLES == WBJ_JOINT_DOUBLES && SRBM_JOINT_STOP_DOUBLES == WBJ_STOP_DOUBLES && SRBM_JOINT_RECORD_DOUBLES == WBJ_RECORD_DOUBLES,
+              "include/srbm_rti.h states the joint model's sizes");
+static const char* const JOINTS_NOT_SET = "no joint model is set (srbm_wb_plant_set_joints)";
+// the refusal of a joint model, naming instance, joint and field
+static int check_joints(const std::string& fn, size_t B, const double* joints, const double* stops) {
+    static const char* const names[WBJ_JOINT_DOUBLES] = {"the viscous damping b", "the armature I_a", "the dry friction f_c", "the stiction band v_s", "q_min", "q_max",
+                                                         "the motor time constant T", "reserved"};
+    for (size_t e = 0; e < WBJ_INSTANCE_DOUBLES * B; e++) {
+        const int f = (int)(e % WBJ_JOINT_DOUBLES);
+        const double x = joints[e];
+        const double* c = joints + e - f;
+        const std::string at = fn + ": instance " + std::to_string(e / WBJ_INSTANCE_DOUBLES) + ", joint " + std::to_string(e / WBJ_JOINT_DOUBLES % 12) + ", field " +
+                               std::to_string(f) + " (" + names[f] + "): ";
+        if (std::isnan(x)) return fail(at + "is NaN");
+        if (f == WBJ_QMIN) { if (!(std::isfinite(x) || x < 0.0)) return fail(at + "must be finite or -inf"); }
+        else if (f == WBJ_QMAX) {
+            if (!(std::isfinite(x) || x > 0.0)) return fail(at + "must be finite or +inf");
+            if (!(c[WBJ_QMIN] < x)) return fail(at + "q_min < q_max is required");
+        }
+        else if (f == WBJ_RESERVED) { if (x != 0.0 || std::signbit(x)) return fail(at + "must be 0"); }
+        else if (!std::isfinite(x) || x < 0.0) return fail(at + "must be finite and >= 0");
+        else if (f == WBJ_VS) {
+            if (c[WBJ_FC] > 0.0 && !(x > 0.0)) return fail(at + "must be > 0 where the dry friction f_c is > 0");
+            if (!(c[WBJ_FC] > 0.0) && x != 0.0) return fail(at + "must be 0 where the dry friction f_c is 0");
+        }
+    }
+    for (size_t e = 0; e < WBJ_STOP_DOUBLES * B; e++) {
+        const std::string at = fn + ": instance " + std::to_string(e / WBJ_STOP_DOUBLES) + ", stops, field " + std::to_string(e % WBJ_STOP_DOUBLES) +
+                               (e % 2 ? " (the stop damping d_l): " : " (the stop stiffness k_l): ");
+        if (!std::isfinite(stops[e])) return fail(at + "must be finite");
+        if (e % 2 == 0 && !(stops[e] > 0.0)) return fail(at + "must be > 0");
+        if (e % 2 == 1 && stops[e] < 0.0) return fail(at + "must be >= 0");
+    }
+    return 0;
+}
+int srbm_wb_plant_set_joints(srbm_batch* h, const double* joints, const double* stops) {
+    const std::string fn = "srbm_wb_plant_set_joints";
+    if (!h) return fail(fn + ": bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (!joints) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->d_joints) HIPCHK(hipFree(h->d_joints));
+        h->d_joints = nullptr; h->joints.clear();
+        return 0;
+    }
+    if (!stops) return fail(fn + ": bad arguments (joints without stops)");
+    const size_t B = h->batch;
+    if (check_joints(fn, B, joints, stops)) return -1;
+    Carve c;
+    const auto a = c.add<double>(JOINT_BUF_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    if (!h->d_joints) HIPCHK(hipMalloc(&h->d_joints, a.bytes()));
+    double* dst = c.host(a);
+    std::memset(dst, 0, a.bytes());                                                  // the motor torques and the record at zero
+    std::memcpy(dst, joints, sizeof(double) * WBJ_INSTANCE_DOUBLES * B);
+    std::memcpy(dst + WBJ_INSTANCE_DOUBLES * B, stops, sizeof(double) * WBJ_STOP_DOUBLES * B);
+    h->joints.assign(dst, dst + (WBJ_INSTANCE_DOUBLES + WBJ_STOP_DOUBLES) * B);
+    HIPCHK(hipMemcpyAsync(h->d_joints, dst, a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_get_joints(srbm_batch* h, double* joints, double* stops) {
+    if (!h || !joints || !stops) return fail("srbm_wb_plant_get_joints: bad arguments");
+    if (!h->d_joints) return fail(std::string("srbm_wb_plant_get_joints: ") + JOINTS_NOT_SET);
+    const size_t B = h->batch;
+    std::memcpy(joints, h->joints.data(), sizeof(double) * WBJ_INSTANCE_DOUBLES * B);
+    std::memcpy(stops, h->joints.data() + WBJ_INSTANCE_DOUBLES * B, sizeof(double) * WBJ_STOP_DOUBLES * B);
+    return 0;
+}
+int srbm_wb_plant_get_joint_state(srbm_batch* h, double* js) {
+    if (!h || !js) return fail("srbm_wb_plant_get_joint_state: bad arguments");
+    if (!h->d_joints) return fail(std::string("srbm_wb_plant_get_joint_state: ") + JOINTS_NOT_SET);
+    return fetch(h, {{js, joint_buf(h).js, sizeof(double) * 12 * (size_t)h->batch}});
+}
+int srbm_wb_plant_set_joint_state(srbm_batch* h, const double* js) {
+    const std::string fn = "srbm_wb_plant_set_joint_state";
+    if (!h || !js) return fail(fn + ": bad arguments");
+    if (!h->d_joints) return fail(fn + ": " + JOINTS_NOT_SET);
+    const size_t B = h->batch;
+    for (size_t e = 0; e < 12 * B; e++)
+        if (!std::isfinite(js[e])) return fail(fn + ": instance " + std::to_string(e / 12) + ", joint " + std::to_string(e % 12) + ": the motor torque is not finite");
+    HIPCHK(hipSetDevice(h->device));
+    Carve c;
+    const auto a = c.add<double>(12 * B);
+    if (c.stage(h)) return -1;
+    std::memcpy(c.host(a), js, a.bytes());
+    HIPCHK(hipMemcpyAsync(joint_buf(h).js, c.host(a), a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_get_joint_record(srbm_batch* h, double* jrec) {
+    if (!h || !jrec) return fail("srbm_wb_plant_get_joint_record: bad arguments");
+    if (!h->d_joints) return fail(std::string("srbm_wb_plant_get_joint_record: ") + JOINTS_NOT_SET);
+    return fetch(h, {{jrec, joint_buf(h).jrec, sizeof(double) * WBJ_RECORD_DOUBLES * (size_t)h->batch}});
+}
+int srbm_joint_law_host(int batch, int substeps, double h, const double* joints, const double* stops, const double* cmd, const int* off, const double* q_j,
+                        const double* v_j, double* js_inout, double* tau_out, double* jrec_inout) {
+    const std::string fn = "srbm_joint_law_host";
+    if (batch <= 0 || !joints || !stops || !cmd || !off || !q_j || !v_j || !js_inout || !tau_out) return fail(fn + ": bad arguments");
+    if (substeps < 1 || !std::isfinite(h) || h <= 0.0) return fail(fn + ": substeps >= 1 and a finite h > 0 are required");
+    const size_t B = batch;
+    if (check_joints(fn, B, joints, stops)) return -1;
+    const double hs = h / (double)substeps;
+    for (size_t b = 0; b < B; b++) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        int over = 0;
+        unsigned mask = 0u;
+        for (int s = 0; s < substeps; s++) {
+            unsigned m = 0u;
+            for (int j = 0; j < 12; j++) {
+                const size_t at = ((size_t)s * B + b) * 12 + j;
+                const double* c = joints + (b * 12 + j) * WBJ_JOINT_DOUBLES;
+                double exc, fr, lag;
+                tau_out[at] = srbm_joint_law(c, srbm_joint_alpha(c[WBJ_T], hs), stops[b * WBJ_STOP_DOUBLES], stops[b * WBJ_STOP_DOUBLES + 1], off[b] ? 0.0 : cmd[at],
+                                             q_j[at], v_j[at], js_inout + b * 12 + j, &exc, &fr, &lag);
+                acc[0] = fmax(acc[0], exc); acc[1] = fmax(acc[1], fr); acc[2] = fmax(acc[2], lag);
+                m |= (exc > 0.0 ? 1u : 0u) << j;
+            }
+            over += m != 0u;
+            mask |= m;
+        }
+        if (jrec_inout) srbm_joint_record_fold(jrec_inout + b * WBJ_RECORD_DOUBLES, substeps, over, acc[0], acc[1], acc[2], mask);
+    }
+    return 0;
 }
 // ---- contact feedback from the ground (srbm_contact_feedback.hiph) ----
 static int launch_contact_feedback(srbm_batch* h, const double* time, const double* cs) {

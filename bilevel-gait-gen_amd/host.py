@@ -48,6 +48,8 @@ KMAX, NODES_MAX, RCCL_UNIQUE_ID_BYTES = 32, 101, 128       # SRBM_TRAJ_KMAX, SRB
 FAST_TOL_STEP, FAST_START_MU = 1e-5, 0.1
 # srbm_wb_plant_set_terrain: the most patches per instance, the doubles of a patch (SRBM_TERRAIN_PATCHES, SRBM_TERRAIN_DOUBLES)
 TERRAIN_PATCHES, TERRAIN_DOUBLES = 8, 8
+# srbm_wb_plant_set_joints: the doubles of a joint, of an instance's stops and of its record (SRBM_JOINT_DOUBLES, _STOP_DOUBLES, _RECORD_DOUBLES)
+JOINT_DOUBLES, JOINT_STOP_DOUBLES, JOINT_RECORD_DOUBLES = 8, 2, 8
 # srbm_set_solver_tolerances(gap_abs, gap_rel, feas, max_iter): ClarabelInterface's settings (clarabel_interface.cpp:165-175), which are also what
 # a new batch holds (srbm_batch_create).  srbm_loader re-exports the name as workloads.REFERENCE_SOLVER_SETTINGS
 REFERENCE_SOLVER_SETTINGS = (1e-15, 1e-15, 1e-10, 200)
@@ -253,6 +255,12 @@ int srbm_wb_forward_dynamics_dev(srbm_batch*, dev*, dev*, dev*, dev*, dev*, dev*
 int srbm_wb_fd_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, dev*, dev*)
 int srbm_wb_plant_set_ground(srbm_batch*, double*)
 int srbm_wb_plant_set_terrain(srbm_batch*, double*, int)
+int srbm_wb_plant_set_joints(srbm_batch*, double*, double*)
+int srbm_wb_plant_get_joints(srbm_batch*, double*, double*)
+int srbm_wb_plant_get_joint_state(srbm_batch*, double*)
+int srbm_wb_plant_set_joint_state(srbm_batch*, double*)
+int srbm_wb_plant_get_joint_record(srbm_batch*, double*)
+int srbm_joint_law_host(int, int, double, double*, double*, double*, int*, double*, double*, double*, double*, double*)
 int srbm_wb_plant_get_contact_state(srbm_batch*, double*)
 int srbm_wb_plant_set_contact_state(srbm_batch*, double*)
 int srbm_wb_ground_dynamics(srbm_batch*, double*, double*, double*, double*, double*, double*, int*)

@@ -859,6 +859,69 @@ int srbm_wb_ground_step_dev(srbm_batch* h, int tick, double tick_dt, double* q_d
 #define SRBM_TERRAIN_DOUBLES 8
 int srbm_wb_plant_set_terrain(srbm_batch* h, const double* terrain, int n_patches);
 
+/* ---- a joint model for the torque-driven plant: damping, rotor inertia, friction, range stops, motor lag ----
+ * The torque law of kind 1 commands a torque that acts at once on a frictionless, massless, unbounded joint.  A joint model is a SETTING of plant
+ * kind 1, per instance and per joint, off by default, on all three surfaces (held feet, ground, terrain).  joints[batch][12][8], the joints in this
+ * library's order (control[0..12), q[7..19): FL, FR, RL, RR, each hip, thigh, calf), per joint:
+ *     0  viscous damping b (N m s/rad)       >= 0
+ *     1  armature I_a (kg m^2)               >= 0      the rotor's reflected inertia, added to the joint's diagonal entry of M
+ *     2  dry friction f_c (N m)              >= 0
+ *     3  stiction band v_s (rad/s)           > 0 where f_c > 0, else must be 0: the friction is f_c clamp(v / v_s, +-1)
+ *     4, 5  q_min, q_max (rad)               finite, or -inf / +inf for none; q_min < q_max
+ *     6  motor time constant T (s)           >= 0
+ *     7  reserved                            must be 0
+ * stops[batch][2] = {k_l > 0 (N m/rad), d_l >= 0 (N m s/rad)}: the compliance of every range stop of the instance.
+ * The state of the model is the motor torque js[batch][12] = tau_m.  Per sub-step of hs = h / S and joint j, on the plant's current (q_j, v_j);
+ * every line is one rounded operation, and a term whose coefficient is 0 is SKIPPED, with no arithmetic on it at all:
+ *     cmd     the command of the torque law of kind 1 as it stands, the clamp to the torque limit included; 0 for an instance whose tick returned a
+ *             zero control action (the actuators are off)
+ *     T == 0: tau_m = cmd
+ *     else:   d = cmd - tau_m; ad = alpha d; tau_m = tau_m + ad         s = T + hs; alpha = hs / s, formed once per launch (an "off" instance
+ *                                                                       decays through its lag)
+ *     t = tau_m
+ *     b != 0:    pd = b v; t = t - pd
+ *     f_c != 0:  r = v / v_s; r = fmin(fmax(r, -1), 1); pc = f_c r; t = t - pc
+ *     e = q_min - q;  e > 0:  sl = k_l e; dl = d_l v; sl = sl - dl; sl = fmax(sl, 0); t = t + sl         (the lower stop)
+ *     e = q - q_max;  e > 0:  su = k_l e; du = d_l v; su = su + du; su = fmax(su, 0); t = t - su         (the upper stop; a stop never pulls a
+ *                                                                                                         joint towards itself, as the ground never pulls)
+ *     t is the joint torque of the sub-step
+ * and in the solve of the sub-step M[6 + j][6 + j] = M[6 + j][6 + j] + I_a where I_a != 0, before the factorisation (30 rows with the feet held, 18
+ * on a ground or a terrain).  The transparent model -- b = I_a = f_c = v_s = T = 0 and infinite ranges -- therefore returns the bytes of the plant
+ * without the setting.
+ * The tick record keeps its fields: 58 counts the joints whose COMMAND was clamped, 59 is max |t - tau_ff| with the model's t; no field is added, and
+ * the tick summaries fold such rollouts unchanged.  The model's own record jrec[batch][8], since the state was set:
+ *     0  sub-steps run                        1  sub-steps with any joint beyond its range
+ *     2  the largest excursion beyond a range (rad)
+ *     3  the largest |pd + pc| (N m)          4  the largest |cmd - tau_m|, tau_m after the motor's statement (N m)
+ *     5  bit mask (bit j: joint j) of the joints ever beyond their range, as a double        6, 7  0
+ * What it is NOT: no command delay (the lag is first order); no torque-speed curve; no gear backlash; the friction is a regularised band, not a
+ * constraint (a joint loaded below f_c creeps at v_s load / f_c); the stops are compliant (a joint passes its range by load / k_l).  The sub-step is
+ * explicit: hs must resolve b / (I_link + I_a), f_c / (v_s (I_link + I_a)) and sqrt(k_l / (I_link + I_a)), I_link the link's own inertia about the
+ * joint (DESIGN.md states the limits in numbers for the A1).
+ *
+ * srbm_wb_plant_set_joints: NULL joints removes the setting and frees its buffers.  Refused, naming instance, joint and field, the batch untouched: a
+ * value that is not finite (other than q_min = -inf, q_max = +inf), a value outside its range, q_min >= q_max, a reserved entry that is not 0.  js
+ * and jrec are zero when the setting is made; srbm_wb_plant_set_state resets both; srbm_batch_clone carries setting, state and record.  Kind 0
+ * ignores the setting.  With kind 1 and a joint model set, srbm_controller_advance, srbm_gait_controller_advance and the three _step_dev entries
+ * (srbm_wb_fd_step_dev, srbm_wb_ground_step_dev, on a terrain too) run the full law on the batch's js and jrec and advance them;
+ * srbm_wb_forward_dynamics[_dev] and srbm_wb_ground_dynamics[_dev] take tau as the NET joint torque and add the armature, nothing else
+ * (the kernels of csrc/srbm_wb_joints.hiph).
+ * srbm_wb_plant_get_joints returns the setting; _get_joint_state / _set_joint_state read and write js (set refuses a value that is not finite);
+ * _get_joint_record returns jrec.  All four are refused while no joint model is set.
+ * srbm_joint_law_host: the same function the kernels compile, without a GPU, over recorded sub-steps: cmd, q_j, v_j [substeps][batch][12] are the
+ * command after its clamp and the joint's angle and rate of each sub-step, off[batch] != 0 an instance with its actuators off (cmd is read as 0),
+ * js_inout[batch][12] the motor torques before and after, tau_out[substeps][batch][12] <- t, jrec_inout (may be NULL) [batch][8] folded into. */
+#define SRBM_JOINT_DOUBLES 8
+#define SRBM_JOINT_STOP_DOUBLES 2
+#define SRBM_JOINT_RECORD_DOUBLES 8
+int srbm_wb_plant_set_joints(srbm_batch* h, const double* joints, const double* stops);
+int srbm_wb_plant_get_joints(srbm_batch* h, double* joints, double* stops);
+int srbm_wb_plant_get_joint_state(srbm_batch* h, double* js);
+int srbm_wb_plant_set_joint_state(srbm_batch* h, const double* js);
+int srbm_wb_plant_get_joint_record(srbm_batch* h, double* jrec);
+int srbm_joint_law_host(int batch, int substeps, double h, const double* joints, const double* stops, const double* cmd, const int* off, const double* q_j,
+                        const double* v_j, double* js_inout, double* tau_out, double* jrec_inout);
+
 /* ---- the MPC update of the rollout in full: MPCController::MPCUpdate (controllers/mpc_controller.cpp:299-346) ----
  * Step 3 of srbm_controller_advance is MPC::GetRealTimeUpdate alone.  The reference's update does two more things, both off by default here.
  *

@@ -30,6 +30,10 @@ medians and spreads.
                  measure kernel's launch per tick costs; everything on (mocap every 5 ticks one sample late, pose noise, finite-difference velocity,
                  gyro noise and bias, joint noise, both filters), another rollout, with the iterations of its whole-body QP; and the measure kernel
                  alone (srbm_controller_measure_dev), 200 launches with everything on.  Skipped, with a note, on a library without the setting
+  (j) joints     (e) at S = 4 with a joint model set (srbm_wb_plant_set_joints: the A1's damping, armature, dry friction, ranges from
+                 tests/golden/a1_joint_model.json, a stiction band of 0.1 rad/s, a motor time constant of 2 ms, stops of 200 N m/rad and 2 N m s/rad),
+                 logged, with the model's record; beside (e) this is what the joint model costs.  And its ground step kernel alone, S = 1 and 4,
+                 interleaved with the ground step kernel alone on the same inputs.  Skipped, with a note, on a library without the setting
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -80,6 +84,12 @@ def main():
         sens_transparent = sensors.record()
         sens_all = sensors.record(mocap_ticks=5, mocap_delay=1, sigma_p=1e-3, sigma_r=2e-3, velocity_source=1, sigma_w=0.01, gyro_bias=(0.01, -0.01, 0.005),
                                   sigma_qj=1e-3, sigma_vj=0.05, lpf_base=sensors.lpf_x(40.0, DT), lpf_joints=sensors.lpf_x(100.0, DT))
+    has_joints = hasattr(ControllerRollout, 'set_joints')
+    if has_joints:
+        from srbm_loader import joints as joint_model
+        res.update({'joints_s4_logged': [], 'joint_ground_step_s1': [], 'joint_ground_step_s4': []})
+        a1_joints, _ = joint_model.a1_model(json.load(open(os.path.join(ROOT, 'tests', 'golden', 'a1_joint_model.json'))), 0.1, 2e-3)
+        a1_stops = (200.0, 2.0)
     ground = terrain = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
@@ -185,6 +195,24 @@ def main():
                                              feet_in_contact_mean=float(word['in_contact'].sum(axis=-1).mean()),
                                              slipping_feet_mean=float(word['slipping'].sum(axis=-1).mean()),
                                              feet_off_the_plan_mean=float(word['plan_differs'].sum(axis=-1).mean()))
+        # (j) ... with the A1's joint model
+        if has_joints:
+            g, R = fresh(TICKS + 3)
+            R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
+            R.set_ground(ground)
+            R.set_joints(a1_joints, a1_stops)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res['joints_s4_logged'].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log, jrec = R.tick_log(), R.joint_record()
+            info['joints_s4_logged'] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
+                                            zero_action_ticks=int((log[:, :, G['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, G['qp_iters']].mean()),
+                                            slowest_qp_iterations_mean=float(log[:, :, G['qp_iters']].max(axis=1).mean()),
+                                            breakdown_ticks=int(((log[:, :, G['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
+                                            clamped_ticks=int((log[:, :, G['clamped_joints']] > 0).sum()), substeps=int(jrec[:, 0].sum()),
+                                            substeps_beyond_a_range=int(jrec[:, 1].sum()), max_excursion=float(jrec[:, 2].max()),
+                                            max_friction_torque=float(jrec[:, 3].max()), max_motor_lag=float(jrec[:, 4].max()))
         # (f) ... with contact feedback on
         g, R = fresh(TICKS + 3)
         R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
@@ -307,6 +335,14 @@ def main():
                     signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
                     res['terrain_step_s%d' % S].append(timed(g, ground_step))
                     R.set_terrain(None)
+                if has_joints:          # ... and the joint model's ground step kernel alone: the same entry with the model in force, from the same start
+                    R.set_joints(a1_joints, a1_stops)
+                    q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64)); cs_d.zero_()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    ground_step()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    res['joint_ground_step_s%d' % S].append(timed(g, ground_step))
+                    R.set_joints(None)
             # ... and the publish kernel alone: every instance published, no instance published
             if has_latency:
                 R.set_latency(0.0)
@@ -373,6 +409,8 @@ def main():
         info['terrain'] = 'this library has no terrain: rows (t) skipped'
     if not has_latency:
         info['latency'] = 'this library has no latency setting: rows (l) skipped'
+    if not has_joints:
+        info['joints'] = 'this library has no joint model: rows (j) skipped'
     if not has_sensors:
         info['sensors'] = 'this library has no sensor model: rows (s) skipped'
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,

@@ -1,5 +1,5 @@
 """Imports the modules of bilevel-gait-gen_amd/ (the directory name is not a Python identifier): `host` (ctypes binding of the C-ABI) and
-`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick`, `mpc_period`, `rollout_summary`, `controller_rollout`, `tick_summary` and `sensors` (the entries beside host.py)."""
+`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick`, `mpc_period`, `rollout_summary`, `controller_rollout`, `tick_summary`, `sensors` and `joints` (the entries beside host.py)."""
 import importlib.util
 import os
 import sys
@@ -30,3 +30,4 @@ sys.modules[__name__ + '.rollout_summary'] = rollout_summary
 controller_rollout = sys.modules[__name__ + '.controller_rollout'] = _load('srbm_controller_rollout', 'controller_rollout.py')
 tick_summary = sys.modules[__name__ + '.tick_summary'] = _load('srbm_tick_summary', 'tick_summary.py')
 sensors = sys.modules[__name__ + '.sensors'] = _load('srbm_sensors', 'sensors.py')
+joints = sys.modules[__name__ + '.joints'] = _load('srbm_joints', 'joints.py')
