@@ -28,6 +28,9 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.set_joints(joints, stops)           optional, with set_plant(1, ...): a joint model -- damping, armature, dry friction, range stops, motor lag --
                                           joints[batch][12][8] from srbm_loader.joints.record(...) or joints.a1_model(), stops = (k_l, d_l)
     js = R.joint_state(); jrec = R.joint_record()
+    R.set_wrenches(wrenches.schedule(batch, [[wrenches.event(0.5, 0.15, 'trunk', force=(0, 60, 0))]]))
+                                          optional, with set_plant(1, ...): timed external forces and torques on any body (srbm_loader.wrenches)
+    wrec = R.wrench_record()
     q, v = R.state(); log = R.tick_log(); pub = R.latency_record(); qm, vm = R.measured(); srec = R.sensor_record()"""
 import ctypes as C
 
@@ -58,6 +61,9 @@ _llp = C.POINTER(C.c_longlong)
 SENSOR_DOUBLES, SENSOR_STATE_DOUBLES, SENSOR_RECORD_DOUBLES = 16, 72, 8          # set_sensors: the setting, the state and the record of an instance
 JOINT_DOUBLES, JOINT_STOP_DOUBLES, JOINT_RECORD_DOUBLES = 8, 2, 8                # set_joints: a joint, an instance's stops, its record
 JOINT_RECORD_FIELDS = dict(substeps=0, substeps_beyond_range=1, max_excursion=2, max_friction_torque=3, max_motor_lag=4, joints_beyond_range=5)
+WRENCH_EVENTS, WRENCH_DOUBLES, WRENCH_RECORD_DOUBLES = 8, 16, 8                  # set_wrenches: the most events per instance, an event, the record
+WRENCH_RECORD_FIELDS = dict(substeps=0, substeps_active=1, events_acted=2, max_generalized_force=3, impulse=slice(4, 7))
+FLAG_WRENCH = 16                    # bit 4 of the tick record's flags: a wrench event acted in a sub-step of the tick
 SENSOR_RECORD_FIELDS = dict(ticks=0, samples=1, max_position=2, max_orientation=3, max_linear_velocity=4, max_angular_velocity=5, max_joint_angle=6,
                             max_joint_rate=7)
 
@@ -316,6 +322,50 @@ class ControllerRollout:
         jrec = np.zeros((m.batch, JOINT_RECORD_DOUBLES))
         m._chk(self.L.srbm_wb_plant_get_joint_record(m.h, _d(jrec)))
         return jrec
+
+    # ---- the wrench schedule of the torque-driven plant ----
+    def set_wrenches(self, wrenches):
+        """timed external wrenches on the bodies of the torque-driven plant (srbm_wb_plant_set_wrenches): wrenches[batch][n_events][16], or one
+        [n_events][16] for every instance, 1 <= n_events <= 8 (wrenches.event and wrenches.schedule build them).  None removes the setting"""
+        m = self.mpc
+        if wrenches is None:
+            m._chk(self.L.srbm_wb_plant_set_wrenches(m.h, None, 0))
+            return
+        w = np.asarray(wrenches, float)
+        if w.ndim not in (2, 3) or w.shape[-1] != WRENCH_DOUBLES or (w.ndim == 3 and w.shape[0] != m.batch):
+            raise ValueError('wrenches is [n_events][%d] or [batch][n_events][%d]' % (WRENCH_DOUBLES, WRENCH_DOUBLES))
+        n = w.shape[-2]
+        w = np.ascontiguousarray(np.broadcast_to(w, (m.batch, n, WRENCH_DOUBLES)))
+        m._chk(self.L.srbm_wb_plant_set_wrenches(m.h, _d(w if w.size else np.zeros(1)), n))
+
+    def wrenches(self):
+        """-> wrenches[batch][n_events][16] as set"""
+        m = self.mpc
+        n = C.c_int(0)
+        m._chk(self.L.srbm_wb_plant_get_wrenches(m.h, None, C.byref(n)))
+        w = np.zeros((m.batch, n.value, WRENCH_DOUBLES))
+        m._chk(self.L.srbm_wb_plant_get_wrenches(m.h, _d(w), C.byref(n)))
+        return w
+
+    def wrench_record(self):
+        """-> wrec[batch][8] (WRENCH_RECORD_FIELDS) after the work queued so far"""
+        m = self.mpc
+        wrec = np.zeros((m.batch, WRENCH_RECORD_DOUBLES))
+        m._chk(self.L.srbm_wb_plant_get_wrench_record(m.h, _d(wrec)))
+        return wrec
+
+    def wrench_force(self, time, q):
+        """the generalized force of the events active at time (one number or [batch]: a sub-step time) on q ([19] or [batch][19])
+        -> Q[batch][18], mask[batch] (bit e: event e is active)"""
+        m = self.mpc
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(time, float), (m.batch,)))
+        Q, mask = np.zeros((m.batch, 18)), np.zeros(m.batch, np.int32)
+        m._chk(self.L.srbm_wb_wrench_force(m.h, _d(t), _d(m._bcast(q, 19)), _d(Q), mask.ctypes.data_as(_ip)))
+        return Q, mask
+
+    def wrench_force_dev(self, time, q, Q, mask):
+        """the same on device pointers (ints): time[batch], q[batch][19] -> Q[batch][18], mask[batch] (int32); asynchronous"""
+        self.mpc._chk(self.L.srbm_wb_wrench_force_dev(self.mpc.h, time, q, Q, mask))
 
     # ---- the ground of the torque-driven plant ----
     def set_ground(self, ground):

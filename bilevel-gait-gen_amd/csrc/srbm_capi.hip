@@ -26,6 +26,7 @@
 #include "srbm_wb_ground.hiph"
 #include "srbm_wb_terrain.hiph"
 #include "srbm_wb_joints.hiph"
+#include "srbm_wb_wrench.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_mpc_latency.hiph"
 #include "srbm_sensors.hiph"
@@ -145,6 +146,10 @@ struct srbm_batch {
     // the joint model of the torque-driven plant (srbm_wb_joints.hiph, srbm_wb_plant_set_joints): one allocation, nullptr: no joint model set
     double* d_joints = nullptr;      // joints[batch][12][8], stops[batch][2], js[batch][12], jrec[batch][8]: joint_buf()
     std::vector<double> joints;      // host copy of the caller's joints, then stops
+    // the wrench schedule of the torque-driven plant (srbm_wb_wrench.hiph, srbm_wb_plant_set_wrenches): one allocation, nullptr: no schedule set
+    double* d_wrench = nullptr;      // wrenches[batch][8][16] (padded with empty slots), wrec[batch][8]: wrench_buf()
+    std::vector<double> wrenches;    // host copy of the caller's wrenches[batch][wrench_events][16]
+    int wrench_events = 0;
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -484,7 +489,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
-    (void)hipFree(h->d_sens); (void)hipFree(h->d_joints);
+    (void)hipFree(h->d_sens); (void)hipFree(h->d_joints); (void)hipFree(h->d_wrench);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -530,6 +535,9 @@ static JointBuf joint_buf(const srbm_batch* h) {
     j.joints = h->d_joints; j.stops = j.joints + WBJ_INSTANCE_DOUBLES * B; j.js = j.stops + WBJ_STOP_DOUBLES * B; j.jrec = j.js + 12 * B;
     return j;
 }
+// the buffers of the wrench schedule, one allocation: the events and the record
+enum { WRENCH_BUF_DOUBLES = WBW_INSTANCE_DOUBLES + WBW_RECORD_DOUBLES };
+static SrbmWrenchArgs wrench_buf(const srbm_batch* h) { return SrbmWrenchArgs{h->d_wrench, h->d_wrench + WBW_INSTANCE_DOUBLES * (size_t)h->batch}; }
 static int wb_alloc(srbm_batch* h) {
     const size_t B = h->batch;
     if (!h->d_wb) HIPCHK(hipMalloc(&h->d_wb, sizeof(double) * WB_DOUBLES * B));
@@ -706,6 +714,10 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     h->joints = src->joints;
     if (ok && src->d_joints)
         ok = hipMalloc(&h->d_joints, sizeof(double) * JOINT_BUF_DOUBLES * B) == hipSuccess && cp(h->d_joints, src->d_joints, sizeof(double) * JOINT_BUF_DOUBLES * B);
+    // (... and the wrench schedule with its record)
+    h->wrenches = src->wrenches; h->wrench_events = src->wrench_events;
+    if (ok && src->d_wrench)
+        ok = hipMalloc(&h->d_wrench, sizeof(double) * WRENCH_BUF_DOUBLES * B) == hipSuccess && cp(h->d_wrench, src->d_wrench, sizeof(double) * WRENCH_BUF_DOUBLES * B);
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -2318,6 +2330,7 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     HIPCHK(hipMemcpyAsync(w.v, v, sizeof(double) * 18 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_cs, 0, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch, h->stream));          // no foot in contact
     if (h->d_joints) HIPCHK(hipMemsetAsync(joint_buf(h).js, 0, sizeof(double) * (12 + WBJ_RECORD_DOUBLES) * (size_t)h->batch, h->stream));   // motors at rest, record empty
+    if (h->d_wrench) HIPCHK(hipMemsetAsync(wrench_buf(h).wrec, 0, sizeof(double) * WBW_RECORD_DOUBLES * (size_t)h->batch, h->stream));
     std::vector<double> fb(SRBM_FB_DOUBLES * (size_t)h->batch);                                                   // no touch-down moved
     for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
@@ -2426,6 +2439,9 @@ static int fd_usable(srbm_batch* h, const char* fn) {
 static bool terrain_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_ground && h->d_terrain; }
 // With a joint model in force (joints_in_force) every step and every solve of kind 1 is the joint model's instantiation (srbm_wb_joints.hiph)
 static bool joints_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_joints; }
+// With a wrench schedule in force (wrenches_in_force) every step of kind 1 is the schedule's instantiation (srbm_wb_wrench.hiph), with or without the
+// joint model's law
+static bool wrenches_in_force(const srbm_batch* h) { return h->fd_kind == 1 && h->d_wrench; }
 static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, double* v, double* cs, const double* control, const int* contact, const int* status,
                             const double* qp_sol, double* sol_out, double* time_next, const SrbmTickLogArgs* lg) {
     const double* push = h->push_set ? h->d_push : nullptr;
@@ -2435,7 +2451,23 @@ static int launch_wb_torque(srbm_batch* h, int tick, double tick_dt, double* q, 
     const SrbmGroundArgs ga{h->d_ground, cs};
     const SrbmTickLogArgs l = lg ? *lg : SrbmTickLogArgs{nullptr, nullptr, nullptr, nullptr, 0};
     const dim3 grid(h->batch), block(WBC_THREADS);
-    if (joints_in_force(h)) {
+    if (wrenches_in_force(h)) {
+        const bool jn = joints_in_force(h);
+        const JointBuf jb = jn ? joint_buf(h) : JointBuf{nullptr, nullptr, nullptr, nullptr};
+        const SrbmJointArgs ja{jb.joints, jb.stops, jb.js, jb.jrec};
+        const SrbmWrenchArgs wa = wrench_buf(h);
+        // (LOGGED, JOINTS) -> the instantiation
+        #define WRENCH_STEP(K, ...) do { \
+            if (lg && jn) hipLaunchKernelGGL((K<true, true>), grid, block, 0, h->stream, __VA_ARGS__); \
+            else if (lg) hipLaunchKernelGGL((K<true, false>), grid, block, 0, h->stream, __VA_ARGS__); \
+            else if (jn) hipLaunchKernelGGL((K<false, true>), grid, block, 0, h->stream, __VA_ARGS__); \
+            else hipLaunchKernelGGL((K<false, false>), grid, block, 0, h->stream, __VA_ARGS__); } while (0)
+        if (cs && terrain_in_force(h)) WRENCH_STEP(srbm_k_wb_terrain_wrench_step, h->dp, fa, ga, h->d_terrain, ja, wa, tick, tick_dt, push, q, v, status, time_next, l);
+        else if (cs) WRENCH_STEP(srbm_k_wb_ground_wrench_step, h->dp, fa, ga, ja, wa, tick, tick_dt, push, q, v, status, time_next, l);
+        else WRENCH_STEP(srbm_k_wb_fd_wrench_step, h->dp, fa, ja, wa, tick, tick_dt, push, q, v, status, time_next, l);
+        #undef WRENCH_STEP
+    }
+    else if (joints_in_force(h)) {
         const JointBuf jb = joint_buf(h);
         const SrbmJointArgs ja{jb.joints, jb.stops, jb.js, jb.jrec};
         if (cs && terrain_in_force(h)) {
@@ -2789,6 +2821,116 @@ int srbm_joint_law_host(int batch, int substeps, double h, const double* joints,
             mask |= m;
         }
         if (jrec_inout) srbm_joint_record_fold(jrec_inout + b * WBJ_RECORD_DOUBLES, substeps, over, acc[0], acc[1], acc[2], mask);
+    }
+    return 0;
+}
+// ---- the wrench schedule of the torque-driven plant (srbm_wb_wrench.hiph) ----
+static_assert(SRBM_WRENCH_EVENTS == WBW_EVENTS && SRBM_WRENCH_DOUBLES == WBW_EVENT_DOUBLES && SRBM_WRENCH_RECORD_DOUBLES == WBW_RECORD_DOUBLES,
+              "include/srbm_rti.h states the wrench schedule's sizes");
+static const char* const WRENCHES_NOT_SET = "no wrench schedule is set (srbm_wb_plant_set_wrenches)";
+// the refusal of a wrench schedule, naming instance, event and field
+static int check_wrenches(const std::string& fn, size_t B, const double* wrenches, int n_events) {
+    static const char* const names[WBW_EVENT_DOUBLES] = {"the start t0", "the duration d", "the body", "the frame", "the point r[0]", "the point r[1]", "the point r[2]",
+                                                         "the force[0]", "the force[1]", "the force[2]", "the torque[0]", "the torque[1]", "the torque[2]", "reserved",
+                                                         "reserved", "reserved"};
+    if (n_events < 1 || n_events > WBW_EVENTS) return fail(fn + ": n_events " + std::to_string(n_events) + " (1.." + std::to_string(WBW_EVENTS) + " events per instance)");
+    const size_t per = (size_t)n_events * WBW_EVENT_DOUBLES;
+    for (size_t e = 0; e < per * B; e++) {
+        const int f = (int)(e % WBW_EVENT_DOUBLES);
+        const double x = wrenches[e];
+        const std::string at = fn + ": instance " + std::to_string(e / per) + ", event " + std::to_string(e % per / WBW_EVENT_DOUBLES) + ", field " + std::to_string(f) +
+                               " (" + names[f] + "): ";
+        if (std::isnan(x)) return fail(at + "is NaN");
+        if (f == WBW_D) { if (x < 0.0) return fail(at + "must be >= 0 or +inf (0: an empty slot)"); }
+        else if (!std::isfinite(x)) return fail(at + "must be finite");
+        else if (f == WBW_BODY) { if (!(x >= 0.0 && x <= 12.0 && x == std::floor(x))) return fail(at + "must be an integer 0..12 (0: the trunk, 1 + 3 leg + k)"); }
+        else if (f == WBW_FRAME) { if (x != 0.0 && x != 1.0) return fail(at + "must be 0 (world axes) or 1 (the body's axes)"); }
+        else if (f >= WBW_RESERVED) { if (x != 0.0 || std::signbit(x)) return fail(at + "must be 0"); }
+    }
+    return 0;
+}
+int srbm_wb_plant_set_wrenches(srbm_batch* h, const double* wrenches, int n_events) {
+    const std::string fn = "srbm_wb_plant_set_wrenches";
+    if (!h) return fail(fn + ": bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (!wrenches) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->d_wrench) HIPCHK(hipFree(h->d_wrench));
+        h->d_wrench = nullptr; h->wrenches.clear(); h->wrench_events = 0;
+        return 0;
+    }
+    const size_t B = h->batch;
+    if (check_wrenches(fn, B, wrenches, n_events)) return -1;
+    Carve c;
+    const auto a = c.add<double>(WRENCH_BUF_DOUBLES * B);
+    if (c.stage(h)) return -1;
+    if (!h->d_wrench) HIPCHK(hipMalloc(&h->d_wrench, a.bytes()));
+    double* dst = c.host(a);
+    std::memset(dst, 0, a.bytes());                                                  // empty slots past n_events, the record at zero
+    const size_t per = (size_t)n_events * WBW_EVENT_DOUBLES;
+    for (size_t b = 0; b < B; b++) std::memcpy(dst + WBW_INSTANCE_DOUBLES * b, wrenches + per * b, sizeof(double) * per);
+    h->wrenches.assign(wrenches, wrenches + per * B); h->wrench_events = n_events;
+    HIPCHK(hipMemcpyAsync(h->d_wrench, dst, a.bytes(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_wb_plant_get_wrenches(srbm_batch* h, double* wrenches, int* n_events) {
+    if (!h || !n_events) return fail("srbm_wb_plant_get_wrenches: bad arguments");
+    if (!h->d_wrench) return fail(std::string("srbm_wb_plant_get_wrenches: ") + WRENCHES_NOT_SET);
+    *n_events = h->wrench_events;
+    if (wrenches) std::memcpy(wrenches, h->wrenches.data(), sizeof(double) * h->wrenches.size());
+    return 0;
+}
+int srbm_wb_plant_get_wrench_record(srbm_batch* h, double* wrec) {
+    if (!h || !wrec) return fail("srbm_wb_plant_get_wrench_record: bad arguments");
+    if (!h->d_wrench) return fail(std::string("srbm_wb_plant_get_wrench_record: ") + WRENCHES_NOT_SET);
+    return fetch(h, {{wrec, wrench_buf(h).wrec, sizeof(double) * WBW_RECORD_DOUBLES * (size_t)h->batch}});
+}
+int srbm_wb_wrench_force_dev(srbm_batch* h, const double* time_dev, const double* q_dev, double* Q_dev, int* mask_dev) {
+    if (!h || !time_dev || !q_dev || !Q_dev || !mask_dev) return fail("srbm_wb_wrench_force: bad arguments");
+    if (!h->d_wrench) return fail(std::string("srbm_wb_wrench_force: ") + WRENCHES_NOT_SET);
+    if (need_legs(h) || use_batch(h)) return -1;
+    hipLaunchKernelGGL(srbm_k_wb_wrench_force, dim3(h->batch), dim3(WBC_THREADS), 0, h->stream, h->dp, h->d_wrench, time_dev, q_dev, Q_dev, mask_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_wb_wrench_force(srbm_batch* h, const double* time, const double* q, double* Q_out, int* mask_out) {
+    if (!h || !time || !q || !Q_out || !mask_out) return fail("srbm_wb_wrench_force: bad arguments");
+    if (!h->d_wrench) return fail(std::string("srbm_wb_wrench_force: ") + WRENCHES_NOT_SET);
+    if (need_legs(h)) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t B = h->batch;
+    Carve c;                                          // in: time, q; out: Q, mask
+    const auto it = c.add<double>(B), iq = c.add<double>(19 * B), oq = c.add<double>(WBC_NV * B);
+    const auto om = c.add<int>(B);
+    if (c.stage(h)) return -1;
+    memcpy(c.host(it), time, it.bytes());
+    memcpy(c.host(iq), q, iq.bytes());
+    HIPCHK(hipMemcpyAsync(c.dev(it), c.host(it), Carve::span(it, iq), hipMemcpyHostToDevice, h->stream));
+    if (srbm_wb_wrench_force_dev(h, c.dev(it), c.dev(iq), c.dev(oq), c.dev(om))) return -1;
+    HIPCHK(hipMemcpyAsync(c.host(oq), c.dev(oq), Carve::span(oq, om), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(Q_out, c.host(oq), oq.bytes());
+    memcpy(mask_out, c.host(om), om.bytes());
+    return 0;
+}
+int srbm_wrench_active_host(int n_events, const double* wrenches, int batch, int first_tick, int ticks, double tick_dt, int substeps, int* mask_out) {
+    const std::string fn = "srbm_wrench_active_host";
+    if (batch <= 0 || !wrenches || ticks < 0 || (ticks > 0 && !mask_out)) return fail(fn + ": bad arguments");
+    if (substeps < 1) return fail(fn + ": substeps >= 1 is required");
+    if (check_tick(fn.c_str(), first_tick, tick_dt)) return -1;
+    const size_t B = batch;
+    if (check_wrenches(fn, B, wrenches, n_events)) return -1;
+    const double hs = tick_dt / (double)substeps;
+    for (int k = 0; k < ticks; k++) {
+        const double tk = (double)(first_tick + k) * tick_dt;
+        for (int s = 0; s < substeps; s++) {
+            const double ts = srbm_wrench_substep_time(tk, hs, s);
+            for (size_t b = 0; b < B; b++) {
+                int m = 0;
+                for (int e = 0; e < n_events; e++) m |= (srbm_wrench_active(wrenches + (b * n_events + e) * WBW_EVENT_DOUBLES, ts) ? 1 : 0) << e;
+                mask_out[((size_t)k * substeps + s) * B + b] = m;
+            }
+        }
     }
     return 0;
 }

@@ -261,6 +261,12 @@ int srbm_wb_plant_get_joint_state(srbm_batch*, double*)
 int srbm_wb_plant_set_joint_state(srbm_batch*, double*)
 int srbm_wb_plant_get_joint_record(srbm_batch*, double*)
 int srbm_joint_law_host(int, int, double, double*, double*, double*, int*, double*, double*, double*, double*, double*)
+int srbm_wb_plant_set_wrenches(srbm_batch*, double*, int)
+int srbm_wb_plant_get_wrenches(srbm_batch*, double*, int*)
+int srbm_wb_plant_get_wrench_record(srbm_batch*, double*)
+int srbm_wb_wrench_force(srbm_batch*, double*, double*, double*, int*)
+int srbm_wb_wrench_force_dev(srbm_batch*, dev*, dev*, dev*, dev*)
+int srbm_wrench_active_host(int, double*, int, int, int, double, int, int*)
 int srbm_wb_plant_get_contact_state(srbm_batch*, double*)
 int srbm_wb_plant_set_contact_state(srbm_batch*, double*)
 int srbm_wb_ground_dynamics(srbm_batch*, double*, double*, double*, double*, double*, double*, int*)

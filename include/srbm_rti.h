@@ -922,6 +922,60 @@ int srbm_wb_plant_get_joint_record(srbm_batch* h, double* jrec);
 int srbm_joint_law_host(int batch, int substeps, double h, const double* joints, const double* stops, const double* cmd, const int* off, const double* q_j,
                         const double* v_j, double* js_inout, double* tau_out, double* jrec_inout);
 
+/* ---- timed external wrenches on any body of the torque-driven plant ----
+ * The push above is one momentum impulse per instance, on the base, at one instant.  A wrench schedule is a SETTING of plant kind 1, per instance,
+ * off by default, on all three surfaces (held feet, ground, terrain), with or without a joint model: a shove held for 150 ms, two pushes in one run,
+ * a kick on a shank, a force off the trunk's origin that also turns the robot, a payload dropped on the back at t = 2 s.
+ * wrenches[batch][n_events][16], 1 <= n_events <= SRBM_WRENCH_EVENTS, per event:
+ *     0       t0, start (s)                  finite
+ *     1       d, duration (s)                >= 0 or +inf; d == 0 is an EMPTY slot that never acts
+ *     2       body                           integer 0..12 in SrbmWbcParams::body order: 0 trunk, 1 + 3 leg + k for hip / thigh / calf of FL FR RL RR
+ *     3       frame of force and torque      0 world axes, 1 the body's axes (the wrench turns with the body)
+ *     4..6    point r (m)                    in the body's joint frame, the frame SrbmBody::com is stated in
+ *     7..9    force (N)                      finite
+ *     10..12  torque (N m)                   finite
+ *     13..15  reserved                       must be 0
+ * The rule, every line one rounded operation.  In sub-step s of tick `tick` of period h with S sub-steps:
+ *     hs = h / S;  p = (double)s hs;  ts = tk + p;  te = t0 + d;        event e is ACTIVE iff d != 0 && ts >= t0 && ts < te
+ * with tk = tick h, so a rollout cut anywhere is the same rollout.  For an active event on body (ee, k), or on the trunk, with the kinematics of
+ * the sub-step's q (R, origin: the rotation and the joint centre of the body, or the base's; Rb, pb the base's; ax, c the leg's joint axes and centres):
+ *     x = origin + R r;   F, N the force and torque in world axes (rotated by R where the frame is 1)
+ *     Q[jj] = colb . F;   Q[3 + jj] = (colb x (x - pb)) . F + colb . N                                  colb = column jj of Rb
+ *     Q[6 + 3 ee + jj] = (ax[ee][jj] x (x - c[ee][jj])) . F + ax[ee][jj] . N     for jj <= k of that leg only;   Q = 0 in every other column
+ * -- the stance Jacobian's column formulas with the point in the place of the foot -- the events summed in event order, one fma chain per column, and
+ * b = b + Q on rows 0..17 of the sub-step's right-hand side after its existing statements.  A sub-step of an instance in which NO event is active
+ * runs no arithmetic of the setting on (q, v) or on the right-hand side (no + 0.0 either): a schedule of empty slots, or of events outside the
+ * rollout, returns the bytes of the plant without the setting.  The existing push is untouched and combines with the schedule.
+ * The record wrec[batch][8], since the state was set:
+ *     0  sub-steps run                        1  sub-steps with any event active
+ *     2  bit mask (bit e: event e) of the events that ever acted, as a double
+ *     3  the largest |Q|_inf
+ *     4..6  the delivered linear impulse in world axes: the sum of hs F over the active (event, sub-step) pairs        7  0
+ * The tick record keeps its fields; bit 4 (value 16) of its flags (field 5) is set when an event acted in any sub-step of the tick.
+ * What it is NOT: a rectangular profile only; the force follows the body point but is no contact, so it has no friction and no geometry; an impulse
+ * is a short event of one sub-step; the controller is told nothing; it is not applied under plant kind 0.
+ *
+ * srbm_wb_plant_set_wrenches: NULL wrenches removes the setting and frees its buffers.  Refused, naming instance, event and field, the batch
+ * untouched: a NaN, a value that is not finite (other than d = +inf), d < 0, a body or a frame that is not an integer in range, a reserved entry
+ * that is not 0; n_events out of range.  The record is zero when the setting is made; srbm_wb_plant_set_state zeroes it; srbm_batch_clone carries the
+ * setting and the record.  Kind 0 ignores the setting, as it ignores the joint model.  With kind 1 and a schedule set, srbm_controller_advance,
+ * srbm_gait_controller_advance and the three _step_dev entries apply it and advance the record (the kernels of csrc/srbm_wb_wrench.hiph).
+ * srbm_wb_forward_dynamics[_dev] and srbm_wb_ground_dynamics[_dev] have no time and ignore the setting.
+ * srbm_wb_plant_get_wrenches: *n_events and, where wrenches is not NULL, wrenches[batch][*n_events][16] as set; _get_wrench_record returns wrec.  Both
+ * are refused while no schedule is set.
+ * srbm_wb_wrench_force[_dev]: the generalized force alone, on the function the step compiles: Q_out[batch][18] of the events active at time[batch]
+ * (a sub-step time ts) on q[batch][19], 0 where none is; mask_out[batch] bit e: event e is active.  Needs the leg geometry and a schedule.
+ * srbm_wrench_active_host: the activity rule without a GPU: mask_out[ticks][substeps][batch] of ticks first_tick .. first_tick + ticks - 1. */
+#define SRBM_WRENCH_EVENTS 8
+#define SRBM_WRENCH_DOUBLES 16
+#define SRBM_WRENCH_RECORD_DOUBLES 8
+int srbm_wb_plant_set_wrenches(srbm_batch* h, const double* wrenches, int n_events);
+int srbm_wb_plant_get_wrenches(srbm_batch* h, double* wrenches, int* n_events);
+int srbm_wb_plant_get_wrench_record(srbm_batch* h, double* wrec);
+int srbm_wb_wrench_force(srbm_batch* h, const double* time, const double* q, double* Q_out, int* mask_out);
+int srbm_wb_wrench_force_dev(srbm_batch* h, const double* time_dev, const double* q_dev, double* Q_dev, int* mask_dev);
+int srbm_wrench_active_host(int n_events, const double* wrenches, int batch, int first_tick, int ticks, double tick_dt, int substeps, int* mask_out);
+
 /* ---- the MPC update of the rollout in full: MPCController::MPCUpdate (controllers/mpc_controller.cpp:299-346) ----
  * Step 3 of srbm_controller_advance is MPC::GetRealTimeUpdate alone.  The reference's update does two more things, both off by default here.
  *

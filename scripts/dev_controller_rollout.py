@@ -34,6 +34,11 @@ medians and spreads.
                  tests/golden/a1_joint_model.json, a stiction band of 0.1 rad/s, a motor time constant of 2 ms, stops of 200 N m/rad and 2 N m s/rad),
                  logged, with the model's record; beside (e) this is what the joint model costs.  And its ground step kernel alone, S = 1 and 4,
                  interleaved with the ground step kernel alone on the same inputs.  Skipped, with a note, on a library without the setting
+  (w) wrenches   (e) at S = 4 with a wrench schedule set (srbm_wb_plant_set_wrenches), logged, with the schedule's record: eight events that never act
+                 (beside (e): the event load and the activity test); one event always active (5 N on the trunk, off its origin); eight always
+                 active (1.5 N each on eight bodies, world and body frames in turn, with torques) -- the last two are other rollouts.  And the
+                 schedule's ground step kernel alone with each of the three, S = 1 and 4, interleaved with the ground step kernel alone on the same
+                 inputs.  Skipped, with a note, on a library without the setting
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -90,6 +95,16 @@ def main():
         res.update({'joints_s4_logged': [], 'joint_ground_step_s1': [], 'joint_ground_step_s4': []})
         a1_joints, _ = joint_model.a1_model(json.load(open(os.path.join(ROOT, 'tests', 'golden', 'a1_joint_model.json'))), 0.1, 2e-3)
         a1_stops = (200.0, 2.0)
+    has_wrenches = hasattr(ControllerRollout, 'set_wrenches')
+    if has_wrenches:
+        from srbm_loader import wrenches as wr
+        schedules = {'never': [wr.event(1e3, np.inf, i) for i in range(8)],
+                     'one': [wr.event(0.0, np.inf, 'trunk', point=(0.05, 0.0, 0.02), force=(0.0, 5.0, 0.0))],
+                     'eight': [wr.event(0.0, np.inf, 1 + (5 * i) % 12 if i else 0, point=(0.02, 0.01, -0.03), force=(1.5 * (-1) ** i, 0.5, -0.5),
+                                        torque=(0.0, 0.05, 0.02), frame='body' if i % 2 else 'world') for i in range(8)]}
+        schedules = {k: wr.schedule(B, [v]) for k, v in schedules.items()}
+        for k in schedules:
+            res.update({'wrench_%s_s4_logged' % k: [], 'wrench_%s_ground_step_s1' % k: [], 'wrench_%s_ground_step_s4' % k: []})
     ground = terrain = None
     kp, kd, lim = np.full(12, 20.0), np.full(12, 0.5), np.asarray(cfg['torque_bounds'], float)
     info = {}
@@ -213,6 +228,24 @@ def main():
                                             clamped_ticks=int((log[:, :, G['clamped_joints']] > 0).sum()), substeps=int(jrec[:, 0].sum()),
                                             substeps_beyond_a_range=int(jrec[:, 1].sum()), max_excursion=float(jrec[:, 2].max()),
                                             max_friction_torque=float(jrec[:, 3].max()), max_motor_lag=float(jrec[:, 4].max()))
+        # (w) ... with a wrench schedule: never active, one event always active, eight always active
+        for k, W in schedules.items() if has_wrenches else ():
+            name = 'wrench_%s_s4_logged' % k
+            g, R = fresh(TICKS + 3)
+            R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
+            R.set_ground(ground)
+            R.set_wrenches(W)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            R.advance(0, 3, TPU, DT)
+            signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+            res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+            log, wrec = R.tick_log(), R.wrench_record()
+            info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), base_height_range=[float(log[:, :, 8].min()), float(log[:, :, 8].max())],
+                              zero_action_ticks=int((log[:, :, G['qp_status']] > 1).sum()), mean_qp_iterations=float(log[:, :, G['qp_iters']].mean()),
+                              slowest_qp_iterations_mean=float(log[:, :, G['qp_iters']].max(axis=1).mean()),
+                              breakdown_ticks=int(((log[:, :, G['flags']].astype(int) & FLAG_BREAKDOWN) != 0).sum()),
+                              ticks_with_an_event=int(((log[:, :, G['flags']].astype(int) & 16) != 0).sum()), substeps=int(wrec[:, 0].sum()),
+                              substeps_active=int(wrec[:, 1].sum()), max_generalized_force=float(wrec[:, 3].max()))
         # (f) ... with contact feedback on
         g, R = fresh(TICKS + 3)
         R.set_plant(PLANT_TORQUE_DRIVEN, kp, kd, lim, 4)
@@ -343,6 +376,14 @@ def main():
                     signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
                     res['joint_ground_step_s%d' % S].append(timed(g, ground_step))
                     R.set_joints(None)
+                for k, W in schedules.items() if has_wrenches else ():          # ... and the schedule's ground step kernel alone, likewise
+                    R.set_wrenches(W)
+                    q_d.copy_(torch.tensor(q0, **f64)); v_d.copy_(torch.tensor(v0, **f64)); cs_d.zero_()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    ground_step()
+                    signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                    res['wrench_%s_ground_step_s%d' % (k, S)].append(timed(g, ground_step))
+                    R.set_wrenches(None)
             # ... and the publish kernel alone: every instance published, no instance published
             if has_latency:
                 R.set_latency(0.0)
@@ -411,6 +452,8 @@ def main():
         info['latency'] = 'this library has no latency setting: rows (l) skipped'
     if not has_joints:
         info['joints'] = 'this library has no joint model: rows (j) skipped'
+    if not has_wrenches:
+        info['wrenches'] = 'this library has no wrench schedule: rows (w) skipped'
     if not has_sensors:
         info['sensors'] = 'this library has no sensor model: rows (s) skipped'
     print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res, ms_per_tick_median=med,
