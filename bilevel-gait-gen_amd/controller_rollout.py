@@ -31,6 +31,8 @@ tests/test_abi_prototypes.py keeps the method list of host.BatchMPC as it stands
     R.set_wrenches(wrenches.schedule(batch, [[wrenches.event(0.5, 0.15, 'trunk', force=(0, 60, 0))]]))
                                           optional, with set_plant(1, ...): timed external forces and torques on any body (srbm_loader.wrenches)
     wrec = R.wrench_record()
+    R.set_commands(commands.stack([[commands.hold(0.0, des12), commands.walk(0.5, 0.3, 0.0, mass, des12)]]))
+                                          optional: the tracking target over time (srbm_loader.commands); crec = R.command_record()
     q, v = R.state(); log = R.tick_log(); pub = R.latency_record(); qm, vm = R.measured(); srec = R.sensor_record()"""
 import ctypes as C
 
@@ -64,6 +66,8 @@ JOINT_RECORD_FIELDS = dict(substeps=0, substeps_beyond_range=1, max_excursion=2,
 WRENCH_EVENTS, WRENCH_DOUBLES, WRENCH_RECORD_DOUBLES = 8, 16, 8                  # set_wrenches: the most events per instance, an event, the record
 WRENCH_RECORD_FIELDS = dict(substeps=0, substeps_active=1, events_acted=2, max_generalized_force=3, impulse=slice(4, 7))
 FLAG_WRENCH = 16                    # bit 4 of the tick record's flags: a wrench event acted in a sub-step of the tick
+COMMAND_EVENTS, COMMAND_DOUBLES, COMMAND_STATE_DOUBLES, COMMAND_RECORD_DOUBLES = 8, 28, 4, 32     # set_commands: events per instance, an event, state, record
+COMMAND_RECORD_FIELDS = dict(updates=0, index=1, events_begun=2, latch_time=3, anchor=slice(4, 6), max_distance=6, sum_sq_distance=7, des=slice(8, 20))
 SENSOR_RECORD_FIELDS = dict(ticks=0, samples=1, max_position=2, max_orientation=3, max_linear_velocity=4, max_angular_velocity=5, max_joint_angle=6,
                             max_joint_rate=7)
 
@@ -366,6 +370,62 @@ class ControllerRollout:
     def wrench_force_dev(self, time, q, Q, mask):
         """the same on device pointers (ints): time[batch], q[batch][19] -> Q[batch][18], mask[batch] (int32); asynchronous"""
         self.mpc._chk(self.L.srbm_wb_wrench_force_dev(self.mpc.h, time, q, Q, mask))
+
+    # ---- timed motion commands ----
+    def set_commands(self, cmds):
+        """the tracking target over time (srbm_controller_set_commands): cmds[batch][n_events][28], or one [n_events][28] for every instance,
+        n_events <= 8 (srbm_loader.commands.hold / walk / stack build them).  None, or no events, removes the setting"""
+        m = self.mpc
+        if cmds is None:
+            m._chk(self.L.srbm_controller_set_commands(m.h, None, 0))
+            return
+        c = np.asarray(cmds, float)
+        if c.ndim not in (2, 3) or c.shape[-1] != COMMAND_DOUBLES or (c.ndim == 3 and c.shape[0] != m.batch):
+            raise ValueError('cmds is [n_events][%d] or [batch][n_events][%d]' % (COMMAND_DOUBLES, COMMAND_DOUBLES))
+        n = c.shape[-2]
+        c = np.ascontiguousarray(np.broadcast_to(c, (m.batch, n, COMMAND_DOUBLES)))
+        m._chk(self.L.srbm_controller_set_commands(m.h, _d(c if c.size else np.zeros(1)), n))
+
+    def commands(self):
+        """-> cmds[batch][n_events][28] as set ([batch][0][28]: none set)"""
+        m = self.mpc
+        n = C.c_int(0)
+        m._chk(self.L.srbm_controller_get_commands(m.h, None, C.byref(n)))
+        c = np.zeros((m.batch, n.value, COMMAND_DOUBLES))
+        if n.value:
+            m._chk(self.L.srbm_controller_get_commands(m.h, _d(c), C.byref(n)))
+        return c
+
+    def command_state(self):
+        """-> cstate[batch][4] = latched event (-1: none), anchor x, anchor y, latch time, after the work queued so far"""
+        m = self.mpc
+        s = np.zeros((m.batch, COMMAND_STATE_DOUBLES))
+        m._chk(self.L.srbm_controller_get_command_state(m.h, _d(s)))
+        return s
+
+    def set_command_state(self, cstate):
+        m = self.mpc
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(cstate, float), (m.batch, COMMAND_STATE_DOUBLES)))
+        m._chk(self.L.srbm_controller_set_command_state(m.h, _d(s)))
+
+    def command_record(self):
+        """-> crec[batch][32] (COMMAND_RECORD_FIELDS) after the work queued so far"""
+        m = self.mpc
+        r = np.zeros((m.batch, COMMAND_RECORD_DOUBLES))
+        m._chk(self.L.srbm_controller_get_command_record(m.h, _d(r)))
+        return r
+
+    def command_costs(self):
+        """-> w[batch][12], Phi_w[batch][12] of the records on the device after the work queued so far: what the last command wrote, or the host's"""
+        m = self.mpc
+        w, pw = np.zeros((m.batch, 12)), np.zeros((m.batch, 12))
+        m._chk(self.L.srbm_controller_get_command_costs(m.h, _d(w), _d(pw)))
+        return w, pw
+
+    def command_dev(self, time, state):
+        """the command kernel alone on device pointers (ints): time[batch], state[batch][13]; asynchronous.  Its place in a host-driven chain is
+        before get_real_time_update_dev"""
+        self.mpc._chk(self.L.srbm_controller_command_dev(self.mpc.h, time, state))
 
     # ---- the ground of the torque-driven plant ----
     def set_ground(self, ground):

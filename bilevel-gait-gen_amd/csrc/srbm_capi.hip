@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -27,6 +28,7 @@
 #include "srbm_wb_terrain.hiph"
 #include "srbm_wb_joints.hiph"
 #include "srbm_wb_wrench.hiph"
+#include "srbm_command.hiph"
 #include "srbm_contact_feedback.hiph"
 #include "srbm_mpc_latency.hiph"
 #include "srbm_sensors.hiph"
@@ -150,6 +152,11 @@ struct srbm_batch {
     double* d_wrench = nullptr;      // wrenches[batch][8][16] (padded with empty slots), wrec[batch][8]: wrench_buf()
     std::vector<double> wrenches;    // host copy of the caller's wrenches[batch][wrench_events][16]
     int wrench_events = 0;
+    // the command schedule of the rollout (srbm_command.hiph, srbm_controller_set_commands): one allocation, nullptr: no schedule set
+    double* d_cmd = nullptr;         // cmds[batch][cmd_events][28], cstate[batch][4], crec[batch][32]: cmd_buf()
+    std::vector<double> cmds;        // host copy of the caller's cmds
+    std::vector<double> cmd_init;    // host image of state and record after a reset (the source of the asynchronous copy that resets them)
+    int cmd_events = 0;
 };
 static int batch_scratch(srbm_batch* h, size_t bytes, void** out) {
     if (bytes > h->scratch_bytes) {
@@ -489,7 +496,7 @@ static void free_batch(srbm_batch* h) {
     (void)hipFree(h->d_fd_act); (void)hipFree(h->d_fd_bodies);
     (void)hipFree(h->d_ground); (void)hipFree(h->d_terrain); (void)hipFree(h->d_cs); (void)hipFree(h->d_fb);
     (void)hipFree(h->pub_insts); (void)hipFree(h->d_lat); (void)hipFree(h->d_pub);
-    (void)hipFree(h->d_sens); (void)hipFree(h->d_joints); (void)hipFree(h->d_wrench);
+    (void)hipFree(h->d_sens); (void)hipFree(h->d_joints); (void)hipFree(h->d_wrench); (void)hipFree(h->d_cmd);
     for (auto e : h->ev_start) (void)hipEventDestroy(e);
     for (auto e : h->ev_stop) (void)hipEventDestroy(e);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -538,6 +545,14 @@ static JointBuf joint_buf(const srbm_batch* h) {
 // the buffers of the wrench schedule, one allocation: the events and the record
 enum { WRENCH_BUF_DOUBLES = WBW_INSTANCE_DOUBLES + WBW_RECORD_DOUBLES };
 static SrbmWrenchArgs wrench_buf(const srbm_batch* h) { return SrbmWrenchArgs{h->d_wrench, h->d_wrench + WBW_INSTANCE_DOUBLES * (size_t)h->batch}; }
+// the buffers of the command schedule, one allocation: the events, the state and the record
+struct CmdBuf { double *cmds, *cstate, *crec; };
+static size_t cmd_buf_doubles(const srbm_batch* h) { return ((size_t)h->cmd_events * CMD_EVENT_DOUBLES + CMD_STATE_DOUBLES + CMD_REC_DOUBLES) * (size_t)h->batch; }
+static CmdBuf cmd_buf(const srbm_batch* h) {
+    CmdBuf c;
+    c.cmds = h->d_cmd; c.cstate = c.cmds + (size_t)h->cmd_events * CMD_EVENT_DOUBLES * h->batch; c.crec = c.cstate + CMD_STATE_DOUBLES * (size_t)h->batch;
+    return c;
+}
 static int wb_alloc(srbm_batch* h) {
     const size_t B = h->batch;
     if (!h->d_wb) HIPCHK(hipMalloc(&h->d_wb, sizeof(double) * WB_DOUBLES * B));
@@ -718,6 +733,10 @@ int srbm_batch_clone(const srbm_batch* src, srbm_batch** out) {
     h->wrenches = src->wrenches; h->wrench_events = src->wrench_events;
     if (ok && src->d_wrench)
         ok = hipMalloc(&h->d_wrench, sizeof(double) * WRENCH_BUF_DOUBLES * B) == hipSuccess && cp(h->d_wrench, src->d_wrench, sizeof(double) * WRENCH_BUF_DOUBLES * B);
+    // (... and the command schedule with its state and record)
+    h->cmds = src->cmds; h->cmd_init = src->cmd_init; h->cmd_events = src->cmd_events;
+    if (ok && src->d_cmd)
+        ok = hipMalloc(&h->d_cmd, sizeof(double) * cmd_buf_doubles(src)) == hipSuccess && cp(h->d_cmd, src->d_cmd, sizeof(double) * cmd_buf_doubles(src));
     if (!ok) { fail("srbm_batch_clone: device copy failed"); return bail(); }
     if (upload_params(h)) return bail();
     if (hipStreamSynchronize(h->stream) != hipSuccess) { fail("srbm_batch_clone: synchronisation failed"); return bail(); }
@@ -1402,13 +1421,18 @@ int srbm_gait_get_lp_result(srbm_gait* g, int* lp_status, double* pred_red) {
     const size_t B = g->h->batch;
     return fetch(g->h, {{lp_status, g->lp_status, sizeof(int) * B}, {pred_red, g->pred_red, sizeof(double) * B}});
 }
+// the records of the batch and of its candidates on the device as the host has them
+static int candidate_records_current(srbm_gait* g) {
+    srbm_batch* h = g->h; srbm_batch* ls = g->ls;
+    if (upload_params(h)) return -1;
+    if (g->ls_gen != h->params_gen) { candidate_params(h, ls); g->ls_gen = h->params_gen; }     // costs / tolerances changed since the last line search
+    return upload_params(ls);
+}
 // candidates -> 10*B solves -> argmin + install; inputs already in h->d_state / d_time / d_ee
 static int line_search_core(srbm_gait* g, bool use_ready_mask) {
     srbm_batch* h = g->h; srbm_batch* ls = g->ls;
     const int B = h->batch;
-    if (upload_params(h)) return -1;
-    if (g->ls_gen != h->params_gen) { candidate_params(h, ls); g->ls_gen = h->params_gen; }     // costs / tolerances changed since the last line search
-    if (upload_params(ls)) return -1;
+    if (candidate_records_current(g)) return -1;
     const int* ready = use_ready_mask ? g->ready : nullptr;
     hipLaunchKernelGGL(srbm_k_gait_spawn_candidates, dim3(B * SRBM_LS_SIZE), dim3(128), 0, h->stream, h->dp, h->insts, ls->insts,
                        g->xk, g->step, h->d_state, h->d_time, h->d_ee, ls->d_state, ls->d_time, ls->d_ee, ready);
@@ -1810,7 +1834,12 @@ int srbm_export_qp(srbm_batch* h, int inst, double* A, double* b, double* Pm, do
     const SrbmInst& I = vi[0];
     const SrbmWork& W = vw[0];
     if (refused_for_capacity(I)) return fail(refused_message("srbm_export_qp", inst));
-    const SrbmParams P = inst_params(h, inst);
+    SrbmParams P = inst_params(h, inst);
+    if (h->d_cmd) {          // with a command schedule set the linear costs are the device's: what the last command wrote (srbm_command.hiph)
+        if (use_batch(h)) return -1;
+        const char* const rec = reinterpret_cast<const char*>(h->dp + inst);
+        if (fetch(h, {{P.w, rec + offsetof(SrbmParams, w), sizeof(P.w)}, {P.Phi_w, rec + offsetof(SrbmParams, Phi_w), sizeof(P.Phi_w)}})) return -1;
+    }
     const int N = P.N, n = I.n, m = I.m, nx = (N + 1) * 12, ns = W.n_samp;
     const double dt = P.dt;
     if (A) std::memset(A, 0, sizeof(double) * (size_t)m * n);
@@ -2331,6 +2360,7 @@ int srbm_wb_plant_set_state(srbm_batch* h, const double* q, const double* v) {
     HIPCHK(hipMemsetAsync(h->d_cs, 0, sizeof(double) * WBG_CS_DOUBLES * (size_t)h->batch, h->stream));          // no foot in contact
     if (h->d_joints) HIPCHK(hipMemsetAsync(joint_buf(h).js, 0, sizeof(double) * (12 + WBJ_RECORD_DOUBLES) * (size_t)h->batch, h->stream));   // motors at rest, record empty
     if (h->d_wrench) HIPCHK(hipMemsetAsync(wrench_buf(h).wrec, 0, sizeof(double) * WBW_RECORD_DOUBLES * (size_t)h->batch, h->stream));
+    if (h->d_cmd) HIPCHK(hipMemcpyAsync(cmd_buf(h).cstate, h->cmd_init.data(), sizeof(double) * h->cmd_init.size(), hipMemcpyHostToDevice, h->stream));   // nothing latched
     std::vector<double> fb(SRBM_FB_DOUBLES * (size_t)h->batch);                                                   // no touch-down moved
     for (size_t i = 0; i < fb.size(); i++) fb[i] = i % 2 ? -1.0 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_fb, fb.data(), sizeof(double) * fb.size(), hipMemcpyHostToDevice, h->stream));
@@ -2958,6 +2988,142 @@ int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, 
     if (use_batch(h)) return -1;
     return launch_contact_feedback(h, time_dev, cs_dev);
 }
+// ---- timed motion commands (srbm_command.hiph) ----
+static_assert(SRBM_CMD_MAX_EVENTS == CMD_MAX_EVENTS && SRBM_CMD_EVENT_DOUBLES == CMD_EVENT_DOUBLES && SRBM_CMD_STATE_DOUBLES == CMD_STATE_DOUBLES &&
+              SRBM_CMD_REC_DOUBLES == CMD_REC_DOUBLES, "include/srbm_rti.h states the command schedule's sizes");
+int srbm_command_event_doubles(void) { return CMD_EVENT_DOUBLES; }
+int srbm_command_record_doubles(void) { return CMD_REC_DOUBLES; }
+static const char* const CMD_NOT_SET = "no command schedule is set (srbm_controller_set_commands)";
+// the refusal of a command schedule, naming instance, event and field
+static int check_commands(const std::string& fn, size_t B, const double* cmds, int n_events) {
+    if (n_events < 0 || n_events > CMD_MAX_EVENTS) return fail(fn + ": n_events " + std::to_string(n_events) + " (0.." + std::to_string(CMD_MAX_EVENTS) + " events per instance)");
+    if (n_events > 0 && !cmds) return fail(fn + ": bad arguments (NULL cmds)");
+    const size_t per = (size_t)n_events * CMD_EVENT_DOUBLES;
+    for (size_t e = 0; e < per * B; e++) {
+        const int f = (int)(e % CMD_EVENT_DOUBLES), ev = (int)(e % per / CMD_EVENT_DOUBLES);
+        const double x = cmds[e];
+        const char* const name = f == CMD_T0 ? "the start t0" : f == CMD_FLAGS ? "the flags" : f == CMD_LEAD ? "the lead" : f == CMD_RESERVED ? "reserved" :
+                                 f < CMD_RATE ? "des12" : "rate12";
+        const std::string at = fn + ": instance " + std::to_string(e / per) + ", event " + std::to_string(ev) + ", field " + std::to_string(f) + " (" + name + "): ";
+        if (!std::isfinite(x)) return fail(at + "must be finite");
+        if (f == CMD_T0 && ev > 0 && !(x > cmds[e - CMD_EVENT_DOUBLES])) return fail(at + "must ascend strictly from event to event");
+        if (f == CMD_FLAGS && x != 0.0 && x != 1.0) return fail(at + "must be 0 or 1 (bit 0: relative; no other bit)");
+        if (f == CMD_LEAD && x < 0.0) return fail(at + "must be >= 0");
+        if (f == CMD_RESERVED && (x != 0.0 || std::signbit(x))) return fail(at + "must be 0");
+    }
+    return 0;
+}
+static void command_reset_image(std::vector<double>& init, size_t B) {
+    init.assign((CMD_STATE_DOUBLES + CMD_REC_DOUBLES) * B, 0.0);
+    for (size_t b = 0; b < B; b++) { init[CMD_STATE_DOUBLES * b + CMD_S_INDEX] = -1.0; init[CMD_STATE_DOUBLES * B + CMD_REC_DOUBLES * b + CMD_R_INDEX] = -1.0; }
+}
+int srbm_controller_set_commands(srbm_batch* h, const double* cmds, int n_events) {
+    const std::string fn = "srbm_controller_set_commands";
+    if (!h) return fail(fn + ": bad arguments (NULL handle)");
+    const size_t B = h->batch;
+    if (check_commands(fn, B, cmds, n_events)) return -1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));          // (the buffer may be in use, the host image the source of a copy under way)
+    if (h->d_cmd) HIPCHK(hipFree(h->d_cmd));
+    h->d_cmd = nullptr; h->cmds.clear(); h->cmd_init.clear(); h->cmd_events = 0;
+    params_changed(h);                                // the host's base costs are back on the device before anything else runs
+    if (n_events == 0) return 0;
+    const size_t per = (size_t)n_events * CMD_EVENT_DOUBLES;
+    h->cmd_events = n_events;
+    h->cmds.assign(cmds, cmds + per * B);
+    command_reset_image(h->cmd_init, B);
+    HIPCHK(hipMalloc(&h->d_cmd, sizeof(double) * cmd_buf_doubles(h)));
+    const CmdBuf c = cmd_buf(h);
+    HIPCHK(hipMemcpyAsync(c.cmds, h->cmds.data(), sizeof(double) * per * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(c.cstate, h->cmd_init.data(), sizeof(double) * h->cmd_init.size(), hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_controller_get_commands(srbm_batch* h, double* cmds, int* n_events) {
+    if (!h || !n_events) return fail("srbm_controller_get_commands: bad arguments");
+    *n_events = h->cmd_events;
+    if (cmds && h->d_cmd) std::memcpy(cmds, h->cmds.data(), sizeof(double) * h->cmds.size());
+    return 0;
+}
+int srbm_controller_get_command_state(srbm_batch* h, double* cstate) {
+    if (!h || !cstate) return fail("srbm_controller_get_command_state: bad arguments");
+    if (!h->d_cmd) return fail(std::string("srbm_controller_get_command_state: ") + CMD_NOT_SET);
+    return fetch(h, {{cstate, cmd_buf(h).cstate, sizeof(double) * CMD_STATE_DOUBLES * (size_t)h->batch}});
+}
+int srbm_controller_set_command_state(srbm_batch* h, const double* cstate) {
+    const std::string fn = "srbm_controller_set_command_state";
+    if (!h || !cstate) return fail(fn + ": bad arguments");
+    if (!h->d_cmd) return fail(fn + ": " + CMD_NOT_SET);
+    for (size_t i = 0; i < CMD_STATE_DOUBLES * (size_t)h->batch; i++) {
+        const double x = cstate[i];
+        if (!std::isfinite(x)) return fail(fn + ": instance " + std::to_string(i / CMD_STATE_DOUBLES) + ", field " + std::to_string(i % CMD_STATE_DOUBLES) + ": must be finite");
+        if (i % CMD_STATE_DOUBLES == CMD_S_INDEX && !(x >= -1.0 && x < (double)h->cmd_events && x == std::floor(x)))
+            return fail(fn + ": instance " + std::to_string(i / CMD_STATE_DOUBLES) + ": the latched index must be an integer -1.." + std::to_string(h->cmd_events - 1));
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(cmd_buf(h).cstate, cstate, sizeof(double) * CMD_STATE_DOUBLES * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+    return srbm_synchronize(h);
+}
+int srbm_controller_get_command_record(srbm_batch* h, double* crec) {
+    if (!h || !crec) return fail("srbm_controller_get_command_record: bad arguments");
+    if (!h->d_cmd) return fail(std::string("srbm_controller_get_command_record: ") + CMD_NOT_SET);
+    return fetch(h, {{crec, cmd_buf(h).crec, sizeof(double) * CMD_REC_DOUBLES * (size_t)h->batch}});
+}
+// w and Phi_w of the records on the device (no schedule is needed: without one they are the host's)
+int srbm_controller_get_command_costs(srbm_batch* h, double* w, double* Phi_w) {
+    if (!h || !w || !Phi_w) return fail("srbm_controller_get_command_costs: bad arguments");
+    if (use_batch(h)) return -1;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const char* const base = reinterpret_cast<const char*>(h->dp);
+    HIPCHK(hipMemcpy2D(w, sizeof(double) * 12, base + offsetof(SrbmParams, w), sizeof(SrbmParams), sizeof(double) * 12, h->batch, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(Phi_w, sizeof(double) * 12, base + offsetof(SrbmParams, Phi_w), sizeof(SrbmParams), sizeof(double) * 12, h->batch, hipMemcpyDeviceToHost));
+    return 0;
+}
+// the command kernel before an MPC update at time[batch] on state[batch][13]; ls: nullptr, or the candidate batch of the gait handle that drives h
+static int launch_command(srbm_batch* h, srbm_batch* ls, const double* time, const double* state) {
+    const CmdBuf c = cmd_buf(h);
+    hipLaunchKernelGGL(srbm_k_command, dim3(h->batch), dim3(CMD_THREADS), 0, h->stream, h->dp, ls ? ls->dp : nullptr, h->batch, c.cmds, h->cmd_events, time, state,
+                       c.cstate, c.crec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int srbm_controller_command_dev(srbm_batch* h, const double* time_dev, const double* state_dev) {
+    if (!h || !time_dev || !state_dev) return fail("srbm_controller_command_dev: bad arguments");
+    if (!h->d_cmd) return fail(std::string("srbm_controller_command_dev: ") + CMD_NOT_SET);
+    if (use_batch(h)) return -1;
+    return launch_command(h, nullptr, time_dev, state_dev);
+}
+int srbm_command_target_host(int n_events, const double* cmds, int batch, const double* Q144, const double* Phi144, int n_updates, const double* times,
+                             const double* states13, double* cstate, double* des12, double* w12, double* Phi_w12, double* crec) {
+    const std::string fn = "srbm_command_target_host";
+    if (batch <= 0 || n_updates < 0 || !Q144 || !Phi144 || !cstate || !crec || (n_updates > 0 && (!times || !states13 || !des12 || !w12 || !Phi_w12)))
+        return fail(fn + ": bad arguments");
+    const size_t B = batch;
+    if (check_commands(fn, B, cmds, n_events)) return -1;
+    const double none = std::numeric_limits<double>::quiet_NaN();
+    for (int u = 0; u < n_updates; u++)
+        for (size_t b = 0; b < B; b++) {
+            const size_t at = (size_t)u * B + b;
+            double* const des = des12 + 12 * at;
+            const double* const evs = cmds + b * n_events * CMD_EVENT_DOUBLES;
+            const double t = times[at];
+            const int index = srbm_cmd_in_force(evs, n_events, t);
+            if (index < 0) {
+                for (int i = 0; i < 12; i++) des[i] = w12[12 * at + i] = Phi_w12[12 * at + i] = none;
+                continue;
+            }
+            const double* const ev = evs + index * CMD_EVENT_DOUBLES;
+            const double x = states13[13 * at], y = states13[13 * at + 1];
+            double ax, ay, unled[2];
+            srbm_cmd_anchor(cstate + CMD_STATE_DOUBLES * b, index, x, y, &ax, &ay);
+            srbm_cmd_target(ev, t, ax, ay, des, unled);
+            for (int i = 0; i < 12; i++) {
+                w12[12 * at + i] = srbm_cmd_cost_row(Q144 + 144 * b, i, des);
+                Phi_w12[12 * at + i] = srbm_cmd_cost_row(Phi144 + 144 * b, i, des);
+            }
+            srbm_cmd_fold(ev, index, t, x, y, ax, ay, des, unled, cstate + CMD_STATE_DOUBLES * b, crec + CMD_REC_DOUBLES * b);
+        }
+    return 0;
+}
 // ---- MPC computation latency (srbm_mpc_latency.hiph) ----
 static const char* const LAT_NOT_SET = "no latency is set (srbm_controller_set_latency)";
 static int check_latency(const char* fn, int batch, const double* lat) {
@@ -3297,6 +3463,9 @@ static int controller_advance(const std::string& fn, srbm_batch* h, srbm_gait* g
                                   w.ee)) return -1;
         // mpc_controller.cpp:322: the contacts measured at t_k -- the ground's state after tick k - 1 -- re-time the plan the update starts from
         if (update && h->contact_fb && launch_contact_feedback(h, time, h->d_cs)) return -1;
+        // the command in force at t_k on the tick's reconstructed state becomes the costs of the update (srbm_command.hiph); the candidates' records
+        // are brought up to date first, so that the line search uploads nothing over what the kernel wrote
+        if (update && h->d_cmd && ((g && candidate_records_current(g)) || launch_command(h, g ? g->ls : nullptr, time, w.state))) return -1;
         const SrbmTickLogArgs lg{h->d_tlog ? h->d_tlog + (size_t)h->tlog_used * B * SRBM_TICK_LOG_DOUBLES : nullptr, w.control, w.ee, w.contact, update ? 1 : 0};
         if (h->fd_kind == 1) {
             if (launch_wb_torque(h, k, tick_dt, w.q, w.v, h->d_ground ? h->d_cs : nullptr, w.control, w.contact, w.status, w.sol, nullptr, w.time + ((k + 1) & 1) * B,

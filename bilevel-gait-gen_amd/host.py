@@ -275,6 +275,16 @@ int srbm_wb_ground_step_dev(srbm_batch*, int, double, dev*, dev*, dev*, dev*, de
 int srbm_controller_set_contact_feedback(srbm_batch*, int)
 int srbm_controller_get_contact_feedback(srbm_batch*, double*)
 int srbm_controller_contact_feedback_dev(srbm_batch*, dev*, dev*)
+int srbm_command_event_doubles()
+int srbm_command_record_doubles()
+int srbm_controller_set_commands(srbm_batch*, double*, int)
+int srbm_controller_get_commands(srbm_batch*, double*, int*)
+int srbm_controller_get_command_state(srbm_batch*, double*)
+int srbm_controller_set_command_state(srbm_batch*, double*)
+int srbm_controller_get_command_record(srbm_batch*, double*)
+int srbm_controller_get_command_costs(srbm_batch*, double*, double*)
+int srbm_controller_command_dev(srbm_batch*, dev*, dev*)
+int srbm_command_target_host(int, double*, int, double*, double*, int, double*, double*, double*, double*, double*, double*, double*)
 int srbm_gait_controller_advance(srbm_gait*, int, int, int, double, int)
 int srbm_controller_set_latency(srbm_batch*, double*)
 int srbm_controller_get_latency_record(srbm_batch*, double*)

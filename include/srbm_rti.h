@@ -1010,6 +1010,71 @@ int srbm_controller_contact_feedback_dev(srbm_batch* h, const double* time_dev, 
  * _sensitivity after a rollout still refuse a last solve that ended by the step rule. */
 int srbm_gait_controller_advance(srbm_gait* g, int first_tick, int ticks, int ticks_per_update, double tick_dt, int gait_opt_freq);
 
+/* ---- timed motion commands: the tracking target of a whole-controller rollout over time, per instance ----
+ * The tracking target is one state_des12 per instance, set on the host (srbm_add_quadratic_tracking_cost[_each] stores w = -Q des,
+ * srbm_set_linear_final_cost[_each] stores Phi_w) and constant for a launch: the reference's apps fix it at construction (apps/mpc_demo.cpp:62-64,
+ * controllers/mpc_controller.cpp:64-67).  A command schedule is a SETTING of the rollout, per instance, off by default: "walk at 0.3 m/s for two
+ * seconds, then stop" in one launch, a sweep of commanded speeds in one batch.
+ * cmds[batch][n_events][28], 1 <= n_events <= SRBM_CMD_MAX_EVENTS, per event:
+ *     0       t0 (s)                         finite, strictly ascending within an instance
+ *     1       flags                          0, or 1: bit 0 = RELATIVE; no other bit
+ *     2       lead (s)                       finite, >= 0
+ *     3       reserved                       must be 0
+ *     4..15   des12                          a tangent state in the layout of srbm_add_quadratic_tracking_cost, finite
+ *     16..27  rate12                         a rate per tangent component, per second, finite
+ * The rule (csrc/srbm_command.hiph), every line one rounded operation.  At the MPC update after tick k, at t = t_k, on the state the tick
+ * reconstructed (with sensors on: from the measurement):
+ *     the event IN FORCE is the last one with t0 <= t.  None: nothing of the instance is touched -- costs, state, record.
+ *     dt = t - t0;  s = dt + lead;  p[i] = rate12[i] s;  des[i] = des12[i] + p[i]
+ *     a relative event: the FIRST update at which it is in force latches (x, y) of that state as the anchor (command state);
+ *         des[0] = des[0] + anchor x;  des[1] = des[1] + anchor y.       An absolute event adds nothing (no + 0.0).  Only x and y can be relative.
+ *     w[i] = -1 * sum_j Q[12 i + j] des[j];   Phi_w[i] = -1 * sum_j Phi[12 i + j] des[j]      j ascending, products and sums rounded separately
+ * -- the arithmetic of srbm_add_quadratic_tracking_cost, so that the setters called with des and -Phi des write the same bytes as the command.
+ * One launch on the batch's stream before the update (after the contact feedback), no copy, no synchronisation.  It writes w and Phi_w of the
+ * instance's record on the device and, under srbm_gait_controller_advance, of the records of its line-search candidates.  The host's costs are
+ * NOT changed: whatever re-uploads the records (a cost setter, a tolerance) between two updates puts the base costs back, which is harmless inside
+ * a rollout because the next update writes the command again; setting or removing the schedule does exactly that.
+ * Command state cstate[batch][4]: index of the latched event (-1: none), anchor x, anchor y (0 for an absolute event), latch time.
+ * Command record crec[batch][32]:
+ *     0  updates at which an event was in force     1  index in force at the last of them (-1: none yet)     2  events begun     3  time of the last latch
+ *     4, 5  the anchor     6  the largest horizontal distance, at an update, between the state's (x, y) and the UN-LED target
+ *     des12 + rate12 (t - t0) (+ anchor)            7  the sum of the squares of that distance             8..19  the des last written     20..31  0
+ * What it is NOT: there is ONE target for the whole horizon, and `lead` is the only look-ahead (no per-node reference); only x and y can be
+ * relative; a rate on an orientation component advances the tangent coordinate linearly; the `ref` band of the rollout and tick summaries still
+ * refers to a fixed target -- the tracking error against a moving target is fields 6 and 7 of this record.
+ * Applied by srbm_controller_advance and srbm_gait_controller_advance alone.  srbm_rti_advance, srbm_closed_loop_advance, srbm_gait_rti_advance and
+ * srbm_gait_closed_loop_advance IGNORE the setting.
+ *
+ * srbm_controller_set_commands: n_events = 0 (cmds may be NULL) removes the setting.  Refused before anything is staged, naming the entry, the
+ * instance, the event and the field, with the setting in force untouched: a NULL handle, n_events outside 0..8, a value that is not finite, a t0
+ * that does not ascend, a flag other than 0 or 1, a negative lead, a reserved double that is not 0.  State and record are zero with both indices -1
+ * when the setting is made.  Setting and removing mark the records changed, so that the host's base costs are on the device before anything runs.
+ * srbm_wb_plant_set_state re-initialises state and record; srbm_batch_clone carries setting, state and record.
+ * srbm_controller_get_commands: *n_events (0: none set) and, where cmds is not NULL, cmds as set.  _get_command_state, _set_command_state (a latched
+ * index -1 .. n_events - 1, finite values) and _get_command_record are refused while no schedule is set.
+ * srbm_controller_get_command_costs: w[batch][12] and Phi_w[batch][12] of the records ON THE DEVICE after the work queued so far; without a
+ * schedule they are the host's.  With a schedule set srbm_export_qp takes its linear costs from the same place.
+ * srbm_controller_command_dev: the kernel alone on time_dev[batch], state_dev[batch][13], for host-driven chains, in the place it has in the
+ * rollout: before srbm_get_real_time_update_dev.  It writes the batch's own records, not a gait handle's candidates.
+ * srbm_command_target_host: the same rule without a GPU, for n_updates updates in turn: times[n_updates][batch], states13[n_updates][batch][13],
+ * Q144 / Phi144[batch][144] -> des12, w12, Phi_w12 [n_updates][batch][12], NaN where no event is in force; cstate[batch][4] and crec[batch][32]
+ * are folded into (initially {-1, 0, 0, 0} and zero with field 1 at -1). */
+#define SRBM_CMD_MAX_EVENTS 8
+#define SRBM_CMD_EVENT_DOUBLES 28
+#define SRBM_CMD_STATE_DOUBLES 4
+#define SRBM_CMD_REC_DOUBLES 32
+int srbm_command_event_doubles(void);
+int srbm_command_record_doubles(void);
+int srbm_controller_set_commands(srbm_batch* h, const double* cmds, int n_events);
+int srbm_controller_get_commands(srbm_batch* h, double* cmds, int* n_events);
+int srbm_controller_get_command_state(srbm_batch* h, double* cstate);
+int srbm_controller_set_command_state(srbm_batch* h, const double* cstate);
+int srbm_controller_get_command_record(srbm_batch* h, double* crec);
+int srbm_controller_get_command_costs(srbm_batch* h, double* w, double* Phi_w);
+int srbm_controller_command_dev(srbm_batch* h, const double* time_dev, const double* state_dev);
+int srbm_command_target_host(int n_events, const double* cmds, int batch, const double* Q144, const double* Phi144, int n_updates, const double* times,
+                             const double* states13, double* cstate, double* des12, double* w12, double* Phi_w12, double* crec);
+
 /* ---- MPC computation latency: the time between the start of an MPC update and the tick from which the control tick sees its result ----
  * The reference's MPC thread (controllers/mpc_controller.cpp:299-398) loops: newest state sample, solve, publish traj_, again; ComputeControlAction
  * (:120-227) evaluates the old traj_ while the solve runs, so every trajectory comes into force one solve late.  A setting of the batch, off by

@@ -39,6 +39,11 @@ medians and spreads.
                  active (1.5 N each on eight bodies, world and body frames in turn, with torques) -- the last two are other rollouts.  And the
                  schedule's ground step kernel alone with each of the three, S = 1 and 4, interleaved with the ground step kernel alone on the same
                  inputs.  Skipped, with a note, on a library without the setting
+  (m) commands   with --commands, these rows ALONE (the others are skipped): (a) logged, and (a) logged with a command schedule set
+                 (srbm_controller_set_commands): one event whose t0 lies beyond the rollout (the schedule never acts: one launch per update that
+                 returns on its test); one event in force that holds the cold start's target; a relative walk at 0.3 m/s with a lead of 0.1 s
+                 (another rollout), each with the record's update count and largest distance.  On a library without the setting (a parent's build
+                 run from a copy of its tree) the logged entry alone, with a note: the parent's figure for the same rollout
 Every launch is under a time limit of its own (an alarm re-armed per call: a launch or a wait that does not return ends the process).
 Prints one JSON line."""
 import json
@@ -60,7 +65,9 @@ from srbm_loader.workloads import config_b_instance, instances
 F = dict(TICK_LOG_FIELDS, **TORQUE_PLANT_LOG_FIELDS)
 G = dict(TICK_LOG_FIELDS, **GROUND_PLANT_LOG_FIELDS)
 B, TICKS, TPU, DT, LIMIT_S = 256, 200, 50, 1e-3, 60.0
-RUNS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+COMMANDS = '--commands' in sys.argv[1:]
+_ARGS = [a for a in sys.argv[1:] if a != '--commands']
+RUNS = int(_ARGS[0]) if _ARGS else 3
 GAIT_TICKS, GAIT_FREQ = 250, 5
 
 
@@ -125,6 +132,39 @@ def main():
         g.synchronize()
         return 1e3 * (time.perf_counter() - tb) / TICKS
 
+    if COMMANDS:          # --commands: rows (m) alone
+        has_commands = hasattr(ControllerRollout, 'set_commands')
+        rows = {'entry_logged': None}
+        if has_commands:
+            from srbm_loader import commands as cmd
+            _, des = host._tracking_cost(cfg)
+            rel = des.copy(); rel[:2] = 0.0
+            rows.update({'commands_never': cmd.stack([[cmd.walk(1e3, 0.3, 0.0, cfg['mass'], rel, lead=0.1)]], batch=B),
+                         'commands_hold': cmd.stack([[cmd.hold(0.0, des)]], batch=B),
+                         'commands_walk': cmd.stack([[cmd.walk(0.0, 0.3, 0.0, cfg['mass'], rel, lead=0.1)]], batch=B)})
+        else:
+            info['commands'] = 'this library has no command schedule: rows (m) are the logged entry alone'
+        res = {k: [] for k in rows}
+        for run in range(RUNS):
+            for name, schedule in rows.items():
+                g, R = fresh(TICKS + 3)
+                if schedule is not None:
+                    R.set_commands(schedule)
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                R.advance(0, 3, TPU, DT)
+                signal.setitimer(signal.ITIMER_REAL, LIMIT_S)
+                res[name].append(timed(g, lambda: R.advance(3, TICKS, TPU, DT)))
+                log = R.tick_log()
+                info[name] = dict(finite=bool(np.all(np.isfinite(R.state()[0]))), mean_qp_iterations=float(log[:, :, F['qp_iters']].mean()),
+                                  base_x_moved_mean=float((R.state()[0][:, 0] - q0[:, 0]).mean()))
+                if schedule is not None:
+                    crec = R.command_record()
+                    info[name].update(updates_with_an_event=int(crec[:, 0].sum()), max_distance=float(crec[:, 6].max()))
+        signal.setitimer(signal.ITIMER_REAL, 0)
+        print(json.dumps(dict(batch=B, ticks=TICKS, ticks_per_update=TPU, tick_dt=DT, runs=RUNS, ms_per_tick_runs=res,
+                              ms_per_tick_median={k: float(np.median(v)) for k, v in res.items()},
+                              spread_ms={k: float(max(v) - min(v)) for k, v in res.items()}, **info)))
+        return
     for run in range(RUNS):
         for name, tl in (('entry', 0), ('entry_logged', TICKS + 3)):
             g, R = fresh(tl)

@@ -1,5 +1,5 @@
 """Imports the modules of bilevel-gait-gen_amd/ (the directory name is not a Python identifier): `host` (ctypes binding of the C-ABI) and
-`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick`, `mpc_period`, `rollout_summary`, `controller_rollout`, `tick_summary`, `sensors`, `joints` and `wrenches` (the entries beside host.py)."""
+`workloads` (seeded instance generators of the BASELINE configurations, sharding), `gait_rollout`, `control_tick`, `mpc_period`, `rollout_summary`, `controller_rollout`, `tick_summary`, `sensors`, `joints`, `wrenches` and `commands` (the entries beside host.py)."""
 import importlib.util
 import os
 import sys
@@ -32,3 +32,4 @@ tick_summary = sys.modules[__name__ + '.tick_summary'] = _load('srbm_tick_summar
 sensors = sys.modules[__name__ + '.sensors'] = _load('srbm_sensors', 'sensors.py')
 joints = sys.modules[__name__ + '.joints'] = _load('srbm_joints', 'joints.py')
 wrenches = sys.modules[__name__ + '.wrenches'] = _load('srbm_wrenches', 'wrenches.py')
+commands = sys.modules[__name__ + '.commands'] = _load('srbm_commands', 'commands.py')
